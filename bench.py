@@ -9,7 +9,12 @@ forward (ResNet-50 encoder -> FPN -> FS-Relation -> decoder -> head -> BCE+dice)
 RCCL gradient all-reduce under DDP, overlapped with backward) + fused SGD update.  Workload =
 BASELINE.json configs[1]: FarSeg ResNet-50 FPN, 3-band 512x512, batch 16 per GPU (weak scaling).
 
-Rank 0 prints ONE JSON line: the contract fields plus
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up (W steps, then three steps each on an empty launch queue), times
+the K steps (nothing else inside them), writes the last step's outputs if --dump-outputs DIR is given, and prints the
+contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  Everything else below is reported only
+under --full:
+  host_unblocked_ms_per_step, per_rank — host time of those three empty-queue steps (median); per-rank host cost and
+                 exposed all-reduce under DDP;
   roofline     — achieved MFMA rate of the dominant kernel family (conv forward + data gradient:
                  conv3x3_halo_x3 / conv1x1_dma / conv_igemm_x3ws / conv_igemm_x3 kernels) = algorithmic FLOPs / HIP-event
                  time of its launches over the timed region, against the peak of the instruction the
@@ -24,7 +29,8 @@ Rank 0 prints ONE JSON line: the contract fields plus
                  step 0 single-stream = each kernel alone = the achieved / frac fields; step K/2 as every other step =
                  the *_overlapped fields)
   cpu_baseline — the CPU oracle (stock PyTorch port of the reference path) timed on this box's host
-                 cores on a bounded sample of the same workload (N=1 only).
+                 cores on a bounded sample of the same workload (N=1 only);
+  library_fp16_gemm, board_power, hip_graph_replay — post-region yardsticks (N=1 only).
 """
 import argparse
 import json
@@ -45,6 +51,7 @@ X3_PASSES = 6                   # bf16 MFMA partial products per fp32 product in
 PEAK_HBM_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E spec peak (6.3 TB/s achievable on a float4 copy)
 GF_FWD_BWD_PER_TILE = 342.7     # conv GFLOP fwd+bwd per 512x512x3 tile, default head
 TILE, BANDS, BATCH = 512, 3, 16
+DUMP_SAMPLE = 1 << 22           # --dump-outputs: model-state values kept (16 MB as float32)
 
 
 def parse():
@@ -57,6 +64,14 @@ def parse():
                         'print what every rank saw (tests/test_bench_launch_cpu.py), and exit')
     p.add_argument('--steps', type=int, default=40)
     p.add_argument('--warmup', type=int, default=5)
+    p.add_argument('--full', action='store_true',
+                   help='also measure what the headline does not need: the event-timed sampled steps and the roofline objects, '
+                        'host_unblocked_ms_per_step / per_rank, the GEMM yardstick, board power, the hip_graph_replay child and '
+                        'the CPU baseline (the --no-* switches below then leave out single ones)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last one computed as DIR/<name>.npy: every tensor the step '
+                        'returned (the losses) and the model state its update left (a fixed, seeded sample of '
+                        f'{DUMP_SAMPLE} values when larger)')
     p.add_argument('--batch', type=int, default=BATCH, help='tiles per GPU (default: the BASELINE config)')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--cpu-baseline-only', action='store_true', help='(internal) time the CPU oracle and print its JSON object')
@@ -81,7 +96,14 @@ def parse():
                    help='BASELINE.json configs[1..4] at N = 1 (per-GPU size): c2 = the headline (default, the only one the '
                         'driver times); c3 = FarSeg++ R50 4-band 1024x1024 batch 8; c4 = ChangeStar (FarSeg-R50 + ChangeMixin) '
                         '2 x (3x512x512) batch 8; c5 = FreeNet 200-band 610x340 scene (padded to 616x344), batch 1')
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:
+        # A plain run is the headline and nothing else: no HIP-event timer inside the timed steps (so no roofline objects),
+        # no hip_graph_replay child, no CPU baseline.  main() also gates on args.full the report of the three empty-queue
+        # steps (host_unblocked_ms_per_step; the steps themselves run either way, as warm-up), the DDP per_rank gather and
+        # exposed-all-reduce events, library_fp16_gemm and board_power.  Under --full the --no-* switches keep their meaning.
+        args.no_kernel_timer = args.no_cpu_baseline = args.no_graph_line = True
+    return args
 
 
 def make_workload(er, cfg, dev, batch, rank):
@@ -132,6 +154,25 @@ def make_batch(dev, batch, rank):
     y = (torch.rand(batch, TILE, TILE, device=dev, generator=g) < 0.3).long()
     y[:, :8, :8] = 255
     return x, y
+
+
+def dump_outputs(path, out, model):
+    """--dump-outputs DIR: what the timed path computed in its last step, as DIR/<name>.npy.  `<loss name>.npy`: every tensor
+    the step returned (float32); `model_state.npy`: the floating-point tensors of model.state_dict() after the step's update
+    (parameters and BatchNorm running statistics, in state_dict order, float32), flattened and concatenated; beyond
+    DUMP_SAMPLE values the same DUMP_SAMPLE positions of that vector every run (torch.randperm, seed 0, sorted)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            v = v.float() if v.is_floating_point() else v.double()
+            np.save(os.path.join(path, k.replace('/', '_') + '.npy'), v.cpu().numpy())
+    flat = torch.cat([t.detach().reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()])
+    if flat.numel() > DUMP_SAMPLE:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(path, 'model_state.npy'), flat.cpu().numpy())
 
 
 def pmc_kernel_launches_per_step(family):
@@ -274,7 +315,7 @@ def graph_replay_line(args):
     per-launch HIP events, so it carries no roofline."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), '--graph', '--steps', str(args.steps), '--warmup', str(max(args.warmup, 4)),
-           '--config', args.config, '--no-cpu-baseline', '--no-graph-line']
+           '--config', args.config, '--full', '--no-cpu-baseline', '--no-graph-line']
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         rows = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -457,10 +498,10 @@ def main():
         args.no_kernel_timer = True
 
         def step():
-            graphed(*inputs)
+            return graphed(*inputs)
     else:
         def step():
-            eager_step(*inputs)
+            return eager_step(*inputs)
 
     def fence():
         torch.cuda.synchronize()
@@ -474,16 +515,20 @@ def main():
     # what enqueuing ONE step costs the host when nothing holds it back: the launch queue is empty (fence above), no event
     # timer, no synchronisation inside; median of three (`host_enqueue_ms_per_step` of the timed loop
     # reads ~ the GPU step time because the full queue back-pressures the host)
+    # These three fenced steps run in every run, plain or --full: the timed region has always begun after W + 3 steps, so
+    # `value` and the state after the last timed step do not depend on --full, and a small --warmup still leaves the first
+    # steps' one-off costs (allocator growth, momentum buffers, first launches) out of the timed steps.  Only --full reports
+    # their host time.
     unblocked = []
     for _ in range(3):
         t_h = time.perf_counter()
         step()
         unblocked.append(time.perf_counter() - t_h)
         fence()
-    host_unblocked_ms = sorted(unblocked)[1] * 1e3
+    host_unblocked_ms = sorted(unblocked)[1] * 1e3 if args.full else None
     # HIP-event timing of the launches costs 2-3 ms per step (an event pair around each of ~250 C-ABI calls), so it
     # samples two steps of the timed region rather than all of them.
-    if use_ddp and hasattr(ddp, 'measure_exposed'):
+    if args.full and use_ddp and hasattr(ddp, 'measure_exposed'):
         ddp.measure_exposed = True
     timer = None if args.no_kernel_timer else timing.KernelTimer()
     # With the weight gradients on their own stream a launch bracketed by events shares the chip with the other
@@ -503,18 +548,18 @@ def main():
         marks.append(time.perf_counter())
         if timer is not None and i in ov_at:
             with timer_ov:
-                step()
+                last_out = step()
             sampled_ov += 1
         elif timer is not None and i in alone_at:
             if two_streams:
                 HF.set_wgrad_stream(False)
             with timer:
-                step()
+                last_out = step()
             if two_streams:
                 HF.set_wgrad_stream(True)
             sampled += 1
         else:
-            step()
+            last_out = step()
     enqueued = time.perf_counter() - t0      # host time to enqueue the K steps (no synchronisation inside the loop)
     if os.environ.get('EVK_BENCH_MARKS'):
         marks.append(time.perf_counter())
@@ -529,6 +574,9 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:   # before anything below runs another step
+        dump_outputs(args.dump_outputs, last_out, model)
+    if use_ddp and args.full:
         # per-rank host cost and exposed all-reduce time: what a rank's Python thread needs to enqueue a
         # step (timed loop / empty queue) and how long its compute stream waited for the last gradient bucket
         mine = torch.tensor([enqueued / args.steps * 1e3, host_unblocked_ms,
@@ -544,7 +592,6 @@ def main():
             'metric': metric, 'value': round(tiles_s, 3 if tiles_s < 100 else 2), 'unit': unit,
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms, 3),
             'host_enqueue_ms_per_step': round(enqueued / args.steps * 1e3, 3),
-            'host_unblocked_ms_per_step': round(host_unblocked_ms, 3),
             'host_cores': host_cores(), 'host_affinity': len(os.sched_getaffinity(0)),
             'host_pinned_cores': args.host_cores,   # (bench.py pins its enqueuing threads by default; the Launcher only under EVK_HOST_CORES,
                                                    #  because DataLoader workers inherit the mask: tiles/s is the same either way — the step is
@@ -565,6 +612,8 @@ def main():
                              '(--mixed_precision bf16; BatchNorm, resampling, losses fp32)') if conv_math == 'bf16'
                        else 'fp32 MFMA (exact fmaf chain)'},
         }
+        if host_unblocked_ms is not None:
+            line['host_unblocked_ms_per_step'] = round(host_unblocked_ms, 3)
         if gf_per_unit is not None:
             line['config']['whole_model_tflops'] = round(tiles_s * gf_per_unit / 1e3 / world, 2)
         if per_rank is not None:
@@ -731,13 +780,13 @@ def main():
                         g1 = a['bytes'] / a['seconds'] / 1e9
                         line['roofline_hbm_' + fam_name].update({'achieved_overlapped': round(g1, 1),
                                                                  'frac_overlapped': round(g1 / PEAK_HBM_GBS, 4)})
-        if world == 1 and not args.graph and 'roofline' in line:
+        if args.full and world == 1 and not args.graph and 'roofline' in line:
             line['roofline']['library_fp16_gemm'] = library_gemm_yardstick(dev)
-        if world == 1 and not args.graph and not args.no_graph_line and not use_ddp:
+        if args.full and world == 1 and not args.graph and not args.no_graph_line and not use_ddp:
             line['board_power'] = board_power_line(step, device_index=local_rank)
-        if world == 1 and not use_ddp and not args.graph and not args.no_graph_line and conv_math == 'f16x2':
+        if args.full and world == 1 and not use_ddp and not args.graph and not args.no_graph_line and conv_math == 'f16x2':
             line['hip_graph_replay'] = graph_replay_line(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline_child()
         out_line = json.dumps(line)
     if use_ddp:

@@ -61,7 +61,7 @@ def main():
                 per[n[:100]] = dict(mfma_busy=round(busy, 4), avg_us=round(r['dur_us'], 1), dispatches_per_pass=r['n'] // max(1, len(paths)))
             if den > 0:
                 out[fam] = dict(mfma_busy=round(num / den, 4), kernels=per)
-        out['method'] = ('rocprofv3 --kernel-trace --pmc <4 counters per pass> on `python bench.py --steps 2 --warmup 1 '
+        out['method'] = ('rocprofv3 --kernel-trace --pmc <4 counters per pass> on `python bench.py --full --steps 2 --warmup 1 '
                          '--no-cpu-baseline --no-kernel-timer` (tools/pmc_bench.sh); mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / '
                          '(32 x SQ_BUSY_CYCLES) per dispatch, averaged per kernel, weighted by kernel time over the family')
         with open(jpath[0], 'w') as f:

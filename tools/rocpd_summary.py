@@ -62,7 +62,7 @@ def main(db_path, out, steps=28, mode='two'):
                 'the other stream are longer than alone, and the families below add up to MORE than the step — compare with the '
                 '`*_overlapped` fields of the bench line; the kernels alone are in `*_kernel_stats_single_stream.md`.**\n\n') +
                 'source: `' + ('EVK_WGRAD_STREAM=0 ' if mode == 'single' else '') +
-                'rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 '
+                'rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 '
                 f'--no-cpu-baseline --no-graph-line` (tools/profile_round.sh; rocpd db summarised by tools/rocpd_summary.py; {steps} steps: 5 warm-up + 3 '
                 f'empty-queue host probes + 20 timed); {sum(r[1] for r in rows)} '
                 f'dispatches, {total / 1e6:.1f} ms of kernel time over a {(span[1] - span[0]) / 1e6:.1f} ms window\n\n')

@@ -1,6 +1,6 @@
 # The multi-GPU scaling curve in one command, for the first box that has more than one MI355X:
 #   bash tools/scale_curve.sh [max_gpus=8] [steps=30] [warmup=10]
-# For N = 1, 2, 4, ... max_gpus: `python bench.py --gpus N` (which starts its N ranks itself, one per GPU, RCCL over xGMI)
+# For N = 1, 2, 4, ... max_gpus: `python bench.py --full --gpus N` (which starts its N ranks itself, one per GPU, RCCL over xGMI)
 #   -> gpurun_out/scale/bench_N.json: the whole-job line with per_rank {host_enqueue, host_unblocked, exposed_allreduce} ms
 # then at N = max_gpus a rocprofv3 --kernel-trace of the same job, rank 0's database summarised by tools/stream_timeline.py
 #   -> gpurun_out/scale/timeline_rank0.txt: which HIP queue RCCL's kernels land on relative to the backward / side / comm
@@ -17,7 +17,7 @@ cd $R
 n=1
 while [ $n -le $MAXN ]; do
   if [ $n -gt $have ]; then echo "N=$n: only $have GPU(s) on this box, stopping"; break; fi
-  python bench.py --gpus $n --steps $STEPS --warmup $WARM --no-cpu-baseline --no-graph-line 2> $O/err_$n.txt | grep '^{"metric"' | tail -1 > $O/bench_$n.json
+  python bench.py --full --gpus $n --steps $STEPS --warmup $WARM --no-cpu-baseline --no-graph-line 2> $O/err_$n.txt | grep '^{"metric"' | tail -1 > $O/bench_$n.json
   [ -s $O/bench_$n.json ] || { echo "N=$n: no bench line (see $O/err_$n.txt)"; tail -5 $O/err_$n.txt; break; }
   last=$n; n=$((n * 2))
 done

@@ -1,5 +1,5 @@
 """Build profiles/rNN_traffic.json from two rocprofv3 PMC passes of bench.py (MI355X_MICROARCH.md §HBM):
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d <dir_fetch> -o r -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timer
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d <dir_fetch> -o r -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timer
     rocprofv3 --kernel-trace --pmc WRITE_SIZE -d <dir_write> -o r -- python bench.py ... (same command)
     python tools/traffic_from_pmc.py <fetch.db> <write.db> profiles/r01_traffic.json
 Counters are KB per dispatch summed over the XCDs; on gfx950 FETCH_SIZE reports half of a wide coalesced
@@ -44,7 +44,7 @@ def main(fetch_db, write_db, out, steps=7):
                     'hbm_bytes_per_launch': round(fb + wb),
                     'kernels': sorted({families.bare(f_name[d]) for d in f_acc if families.family_of(f_name[d]) == fam})}
     res['method'] = __doc__.split('\n\n')[0] if False else (
-        'rocprofv3 --kernel-trace --pmc FETCH_SIZE and, in a separate pass, --pmc WRITE_SIZE on `python bench.py --steps 3 '
+        'rocprofv3 --kernel-trace --pmc FETCH_SIZE and, in a separate pass, --pmc WRITE_SIZE on `python bench.py --full --steps 3 '
         '--warmup 1 --no-cpu-baseline --no-kernel-timer`; counters are KB summed over the 8 XCDs per dispatch; FETCH_SIZE '
         'doubled (gfx950 reports half of a wide coalesced stream, guide §HBM); families as tools/families.py defines them (conv_igemm = every forward / data-gradient '
         'convolution kernel incl. conv1x1_ps; conv_wgrad; bn_*; resample_loss = bilinear_* / nearest2x_* / bce_* / dice_* / ce_*), the kernels '
