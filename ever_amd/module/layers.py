@@ -21,7 +21,8 @@ Identity = nn.Identity
 class Conv2d(nn.Conv2d):
     """nn.Conv2d (zero padding) on the MFMA implicit-GEMM kernels; weight kept OHWI in memory.  groups > 1 (the ResNeXt
     bodies of reference _resnets.py:291-324) runs as a dense convolution with the block-diagonal weight
-    (HF.grouped_dense_weight: exact zeros outside the groups)."""
+    (HF.grouped_dense_weight: exact zeros outside the groups).  A depthwise convolution (groups == in == out channels,
+    reference ops.py:25-42) within the depthwise kernels' scope runs on them instead (HF.depthwise_conv2d)."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -29,7 +30,11 @@ class Conv2d(nn.Conv2d):
         self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
 
     def forward(self, x, relu=False, bn_stats=False):
-        """bn_stats: a training-mode BatchNorm consumes the result next (hip/conv.py:conv2d)"""
+        """bn_stats: a training-mode BatchNorm consumes the result next (hip/conv.py:conv2d); the depthwise kernels
+        leave no statistics, and that BatchNorm then computes its own"""
+        if self.groups != 1 and HF.depthwise_in_scope(self.in_channels, self.out_channels, self.groups, self.kernel_size,
+                                                      self.stride, self.dilation):
+            return HF.depthwise_conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation, relu=relu)
         w = self.weight if self.groups == 1 else HF.grouped_dense_weight(self.weight, self.groups)
         y = HF.conv2d(x, w, self.bias, self.stride, self.padding, self.dilation, relu=relu, bn_stats=bn_stats)
         if self._forward_hooks and getattr(y, '_evk_bn_parts', None) is not None and len(y._evk_bn_parts) > 2:
@@ -72,6 +77,9 @@ class BatchNorm2d(nn.BatchNorm2d):
         hip/norm.py:batch_norm_act); any other reader would see raw words."""
         if self.momentum is None:
             raise NotImplementedError('ever_amd BatchNorm2d: cumulative moving average (momentum=None) unsupported')
+        if self.training and x.dim() == 4 and x.shape[0] * x.shape[2] * x.shape[3] == 1:
+            # as torch.nn.functional.batch_norm: one value per channel has no variance (ASPP's pool branch at batch 1)
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size {tuple(x.shape)}')
         training = self.training or (self.running_mean is None)
         if self.training and self.track_running_stats and self.num_batches_tracked is not None:
             # counted on the host and folded into the buffer when it is read (state_dict / checkpoint):

@@ -661,6 +661,27 @@ int evk_ohem_fwd(const float* losses, int64_t n, int64_t keep, float* loss, void
 int evk_ohem_bwd(const float* losses, int64_t n, void* state, const float* grad_scale, float* dlosses,
                  void* stream);
 
+/* ------------------------------------------------------------------ depthwise convolution --- */
+/* nn.Conv2d(C, C, k, groups=C) — reference ops.py:25-31 (DepthwiseConv2d), :34-42 (SeparableConv2d's first
+ * convolution; SeparableConvBlock in deeplabv3p_head.py:36-38).  Exact fp32 FMA on the vector ALUs in every arithmetic
+ * mode (the convolution is HBM-bound).  Descriptor: Cin == Cout = C, C % 4 == 0, kh, kw in 1..7, stride 1 or 2 on each
+ * axis, any dilation, any zero padding; anything else returns EVK_E_UNSUPPORTED before a launch.  w: the [C][1][kh][kw]
+ * parameter ([C][kh][kw] memory); bias may be NULL; flags: EVK_CONV_RELU.  x / y NHWC. */
+int evk_depthwise_fwd(const evk_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
+                      uint32_t flags, void* stream);
+/* Host only: bytes of the per-tile weight / bias gradient records of evk_depthwise_bwd (0 for a descriptor out of scope). */
+size_t evk_depthwise_bwd_workspace_bytes(const evk_conv_desc* d);
+/* Gradients of evk_depthwise_fwd: dx (may be NULL), dw [C][kh][kw] and db [C] (either may be NULL; then x may be NULL
+ * too).  y: the forward's output when it fused the ReLU (the mask), else NULL.  One pass over dy and x writes dx and a
+ * record of dw / db partial sums per tile; a second kernel sums the records in a fixed order (no atomics). */
+int evk_depthwise_bwd(const evk_conv_desc* d, const float* dy, const float* x, const float* y, const float* w,
+                      float* dx, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+/* dst[n][p][c] = src[n][c] for p < HW: F.interpolate of a 1x1 map to any size (bilinear, align_corners=False), which is
+ * an exact broadcast — reference ops.py:96-100 (PoolBlock).  evk_sum_hw is its adjoint: dst[n][c] = sum over p of
+ * src[n][p][c] in a fixed order.  C % 4 == 0. */
+int evk_broadcast_hw(const float* src, float* dst, int32_t N, int64_t HW, int32_t C, void* stream);
+int evk_sum_hw(const float* src, float* dst, int32_t N, int64_t HW, int32_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
