@@ -18,7 +18,7 @@
 //    its own fragments and owns 32 rows x BN/2 columns of the tile.
 // Epilogue: the shared ones of igemm_common.hpp (bias / accumulate (+ ReLU bits) / ReLU / operand-scale slots, or the
 // BatchNorm statistics form through LDS, which reuses the ring).
-#include "igemm_common.hpp"
+#include "conv_route.hpp"
 #include "x3_common.hpp"
 #include "lds_dma.hpp"
 #include <stdlib.h>
@@ -248,70 +248,24 @@ static int launch_c1_pk(IGemmArgs& a, hipStream_t stream) {
   return a.a_packed ? launch_c1<BN, true, NST, WAVES_M>(a, stream) : launch_c1<BN, false, NST, WAVES_M>(a, stream);
 }
 
-bool conv1x1_dma_applicable(const IGemmArgs& a) {
+bool conv1x1_dma_supports(const IGemmArgs& a) {
   if (a.planes != 2 || a.kh != 1 || a.kw != 1 || (a.Cs & 31) != 0 || a.Kpad != a.Cs) return false;
   const unsigned long long sb = (unsigned long long)a.N * a.Hs * a.Ws * a.Cs * 4ull;
   const unsigned long long wb = 2ull * a.Cd * a.Kpad * 2ull;
   return sb < 0x80000000ull && wb < 0x80000000ull;  // 32-bit buffer offsets, kDmaOOB above every valid one
 }
 
-int launch_conv1x1_dma_forced(IGemmArgs& a, int bn, hipStream_t stream) {
-  if (!conv1x1_dma_applicable(a)) {
-    set_error("conv1x1_dma: shape not supported (1x1, Cs %% 32 == 0, f16x2 arithmetic)");
-    return EVK_E_UNSUPPORTED;
+// column tile 256 / 128 / 64 with a ring of three stages (one workgroup per CU), or 128 / 64 with two (two per CU)
+int launch_conv1x1_dma(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
+  EVK_REQUIRE(conv1x1_dma_supports(a), EVK_E_UNSUPPORTED, "conv1x1_dma: shape not supported (1x1, Cs %% 32 == 0, f16x2 arithmetic)");
+  switch (r.bn * 10 + r.stages) {
+    case 2563: return launch_c1_pk<256, 3>(a, stream);
+    case 1283: return launch_c1_pk<128, 3>(a, stream);
+    case 643: return launch_c1_pk<64, 3>(a, stream);
+    case 1282: return launch_c1_pk<128, 2>(a, stream);
+    case 642: return launch_c1_pk<64, 2>(a, stream);
   }
-  if (bn == 256) return launch_c1_pk<256, 3>(a, stream);
-  if (bn == 128) return launch_c1_pk<128, 3>(a, stream);
-  if (bn == 64) return launch_c1_pk<64, 3>(a, stream);
-  // two stages: two workgroups per CU (one's epilogue under the other's loop)
-  if (bn == 2128) return launch_c1_pk<128, 2>(a, stream);
-  return launch_c1_pk<64, 2>(a, stream);
-  // (four-wave forms, 2 x 2 waves of 64 x BN/2 — a third fewer LDS bytes per MFMA — measured behind the eight-wave ones on
-  // every shape: 182-190 vs 178-180 us on 256->256 @128^2; instantiate launch_c1_pk<BN, NST, 2> to try them again)
-}
-
-// returns 1 when this form does not apply (the caller goes on to the register-staged kernels)
-int launch_conv1x1_dma(IGemmArgs& a, hipStream_t stream) {
-  // EVK_C1_DMA: 0 never; 1 (default) where measured faster; 2 wherever the shape allows
-  static const int mode = getenv("EVK_C1_DMA") ? atoi(getenv("EVK_C1_DMA")) : 1;
-  if (mode == 0 || !conv1x1_dma_applicable(a)) return 1;
-  // The three-role persistent form (conv1x1_ps2.hip: loader / compute / store waves, software-pipelined K step) takes the
-  // 128^2-map layers and the short-reduction layers of the 64^2 maps (round 4's two-role persistent kernel, conv1x1_ps.hip,
-  // which it superseded on every shape, was deleted in round 6) — measured (tools/ab_c1sp.py, us, best other
-  // form -> this): 64 -> 256 @128^2 93 -> 78, 256 -> 256 173 -> 152, 256 -> 128 98 -> 83, 128 -> 512 @64^2 52 -> 46; level on
-  // the longer reductions of the 64^2 / 32^2 maps, behind on 2048 -> 512 @16^2 (one tile per workgroup: nothing to overlap).
-  // EVK_C1_PS2: 0 never, 1 (default) by that rule, 2 wherever it applies (tests)
-  static const int ps2_mode = getenv("EVK_C1_PS2") ? atoi(getenv("EVK_C1_PS2")) : 1;
-  if (ps2_mode != 0 && conv1x1_ps2_applicable(a) && a.Cd >= 128) {
-    const int tm = ceil_div(a.M, 128), nk = a.Kpad / BK3;
-    if (ps2_mode == 2 || tm >= 1024 || (tm >= 512 && nk <= 4)) {
-      const int rc = launch_conv1x1_ps2(a, stream);   // (1: the column tiles do not fit this device's CUs per XCD — go on)
-      if (rc != 1) return rc;
-    }
-  }
-  if (mode == 2) return launch_conv1x1_dma_forced(a, a.Cd >= 128 ? 2128 : 2064, stream);
-  // Measured on the FarSeg-R50 one-tap shapes, fp32 and packed operands, with and without the statistics epilogue
-  // (tools/ab_c1dma.py, us, register-staged default -> this kernel): the two-stage ring with TWO workgroups per CU (one's
-  // store burst under the other's loop) is ahead of the three-stage ring at one workgroup per CU and of the default wherever
-  // the output is at least 128 channels wide: 256->256 @128^2 225-244 -> 178-185, 256->128 115-136 -> 104-107, 128->512 @64^2
-  // 62-69 -> 56-60, 512->128 41-50 -> 38-40, 512->256 75-86 -> 70-77, 1024->256 @32^2 36-42 -> 35-39, level on 64->256
-  // (108-138 -> 108-113), 256->1024 and 512->2048; 64-wide outputs stay on the default (256->64: 66-76 vs 72-78).
-  // 16^2 maps: 64-wide column tiles where 128-wide ones leave CUs without a workgroup (2048->512: 47-55 -> 41-50).
-  if (a.Cd < 128) return 1;
-  const long long tm = ceil_div(a.M, 128);
-  int bn = 2128;
-  // (below how many 128-wide tiles the 64-wide ones are taken: swept in the step in round 5, where the chip is shared with the
-  // side stream — 128 / 320 / 640 / 1100 all behind or level with 224)
-  constexpr long long fill_wg = 224;
-  if (tm * ceil_div(a.Cd, 128) < fill_wg) {
-    if (tm * ceil_div(a.Cd, 64) < 224) return 1;   // cannot fill the chip
-    // long reductions on the 16^2 maps (2048 -> 512: 64 steps, one 128 x 64 tile per CU): the software-pipelined form with
-    // loader waves (conv1x1_sp.hip, ring of four) — 42.9 -> 32.8 us, 43.3 -> 33.6 with the statistics epilogue (tools/ab_c1sp.py)
-    static const int sp_mode = getenv("EVK_C1_SP") ? atoi(getenv("EVK_C1_SP")) : 1;
-    if (sp_mode && a.Kpad / BK3 >= 32 && conv1x1_sp_applicable(a)) return launch_conv1x1_sp_forced(a, 64, stream);
-    bn = 2064;
-  }
-  return launch_conv1x1_dma_forced(a, bn, stream);
+  EVK_REQUIRE(false, EVK_E_INVALID, "conv1x1_dma: no %d-wide tile with %d stages", r.bn, r.stages);
 }
 
 }  // namespace evk

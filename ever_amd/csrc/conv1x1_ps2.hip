@@ -22,7 +22,7 @@
 //            nk - 1 slices between those barriers; the last tile after E1.
 // Compile-time ablations (tools/build_variant.sh -DEVK_PS2_ABL=bits): 1 no loader DMA, 4 no compute, 8 no global stores,
 // 16 store waves idle, 32 no staging writes.
-#include "igemm_common.hpp"
+#include "conv_route.hpp"
 #include "x3_common.hpp"
 #include "lds_dma.hpp"
 #include <stdlib.h>
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(64 * kP2Waves) void conv1x1_ps2_kernel(const IGemmA
   const int nmine = grp < p.tiles_m ? (p.tiles_m - grp + ngroups - 1) / ngroups : 0;
   if (nmine <= 0) return;                              // (the whole workgroup: no barrier is left waiting)
   const int n0 = tile_n * BN;
-  const int nk = p.Kpad / BK3;                         // >= 2 (conv1x1_ps2_applicable)
+  const int nk = p.Kpad / BK3;                         // >= 2 (conv1x1_ps2_supports)
   const int G = nmine * nk;                            // global K steps of this workgroup
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem_p2;
   const uint32_t stg0 = lds0 + kP2Ring;
@@ -437,19 +437,18 @@ __global__ __launch_bounds__(64 * kP2Waves) void conv1x1_ps2_kernel(const IGemmA
   close_tile();
 }
 
-bool conv1x1_ps2_applicable(const IGemmArgs& a) {
-  if (!conv1x1_dma_applicable(a)) return false;
+bool conv1x1_ps2_supports(const IGemmArgs& a) {
+  if (!conv1x1_dma_supports(a)) return false;
   const int nk = a.Kpad / BK3;
   // (accumulate epilogues and strided destinations stay on conv1x1_dma.hip: the store waves may not read global memory)
   const int tn = ceil_div(a.Cd, kP2BN);
   return nk >= 2 && (a.Cd & 3) == 0 && a.Cd >= 64 && a.dense_dst && !a.accum && tn <= 32;
 }
 
-int launch_conv1x1_ps2(IGemmArgs& a, hipStream_t stream) {
-  if (!conv1x1_ps2_applicable(a)) {
-    set_error("conv1x1_ps2: launch not supported (1x1, Cs %% 32 == 0, Cs >= 64, Cout %% 4 == 0, dense destination, no accumulate)");
-    return EVK_E_UNSUPPORTED;
-  }
+int launch_conv1x1_ps2(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
+  static_assert(kP2BM == 128 && kP2BN == 128, "conv_route.hip counts this kernel's column tiles as Cd / 128");
+  EVK_REQUIRE(conv1x1_ps2_supports(a) && r.bn == kP2BN, EVK_E_UNSUPPORTED,
+              "conv1x1_ps2: launch not supported (1x1, Cs %% 32 == 0, Cs >= 64, Cout %% 4 == 0, dense destination, no accumulate)");
   a.tiles_m = ceil_div(a.M, kP2BM);
   a.tiles_n = ceil_div(a.Cd, kP2BN);
   // statistics: two records per row tile (one per 64-row half), within evk_conv2d_stats_max_parts' M / 64 + 1
@@ -459,31 +458,12 @@ int launch_conv1x1_ps2(IGemmArgs& a, hipStream_t stream) {
     a.bn_part = a.bn_buf;
     a.bn_parts = 2 * a.tiles_m;
   }
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    set_error("conv1x1_ps2: cannot query the device");
-    return EVK_E_LAUNCH;
-  }
-  static int cus_of[64];                 // per device id (one process may drive devices of different sizes)
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (!cus_of[dev]) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-      set_error("conv1x1_ps2: cannot query the device");
-      return EVK_E_LAUNCH;
-    }
-    cus_of[dev] = prop.multiProcessorCount;
-  }
-  const int cus = cus_of[dev];
   const long long items = (long long)a.tiles_m * a.tiles_n;
-  if (items <= 0 || items > 0x7fffffffLL) {
-    set_error("conv1x1_ps2: bad grid %lld", items);
-    return EVK_E_INVALID;
-  }
+  EVK_REQUIRE(items > 0 && items <= 0x7fffffffLL, EVK_E_INVALID, "conv1x1_ps2: bad grid %lld", items);
   // gridDim / 8 workgroups per XCD, a multiple of tiles_n (the kernel's tile order), at most one workgroup per CU
-  const int slots = (cus / 8) / a.tiles_n * a.tiles_n;
-  if (slots <= 0) return 1;   // (more column tiles than this device has CUs per XCD: not this kernel's launch — the caller falls
-                              // through to the non-persistent forms)
+  // (the planner routes a launch here only when the column tiles fit the device's CUs per XCD)
+  const int slots = device_cus_per_xcd() / a.tiles_n * a.tiles_n;
+  EVK_REQUIRE(slots > 0, EVK_E_INVALID, "conv1x1_ps2: %d column tiles do not fit this device's CUs per XCD", a.tiles_n);
   const int grid = 8 * slots;
   const unsigned long long sb = (unsigned long long)a.N * a.Hs * a.Ws * a.Cs * 4ull;
   const unsigned long long wb = 2ull * a.Cd * a.Kpad * 2ull;

@@ -19,7 +19,7 @@
 //    needs stage kt+1 complete one half step early: ring of NST = 4 stages, NST - 1 in flight;
 //  * no run-time ablation switch inside the loop (compile-time EVK_SP_ABL: 1 no loader DMA, 4 no compute, 8 no stores).
 // Epilogues: the shared ones of igemm_common.hpp; the loader waves end before them (an ended wave is not waited for).
-#include "igemm_common.hpp"
+#include "conv_route.hpp"
 #include "x3_common.hpp"
 #include "lds_dma.hpp"
 #include <stdlib.h>
@@ -279,18 +279,19 @@ static int launch_sp(IGemmArgs& a, hipStream_t stream) {
   return check_launch("conv1x1_sp");
 }
 
-bool conv1x1_sp_applicable(const IGemmArgs& a) { return conv1x1_dma_applicable(a) && a.Kpad / BK3 >= 2; }
+bool conv1x1_sp_supports(const IGemmArgs& a) { return conv1x1_dma_supports(a) && a.Kpad / BK3 >= 2; }
 
-// bn: 128 / 64 = column tile with a ring of four stages; 3128 / 3064 = three stages
-int launch_conv1x1_sp_forced(IGemmArgs& a, int bn, hipStream_t stream) {
-  if (!conv1x1_sp_applicable(a)) {
-    set_error("conv1x1_sp: shape not supported (1x1, Cs %% 32 == 0, Cs >= 64, f16x2 arithmetic)");
-    return EVK_E_UNSUPPORTED;
+// column tile 128 / 64 with a ring of four or three stages
+int launch_conv1x1_sp(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
+  EVK_REQUIRE(conv1x1_sp_supports(a), EVK_E_UNSUPPORTED,
+              "conv1x1_sp: shape not supported (1x1, Cs %% 32 == 0, Cs >= 64, f16x2 arithmetic)");
+  switch (r.bn * 10 + r.stages) {
+    case 1284: return a.a_packed ? launch_sp<128, true, 4>(a, stream) : launch_sp<128, false, 4>(a, stream);
+    case 644: return a.a_packed ? launch_sp<64, true, 4>(a, stream) : launch_sp<64, false, 4>(a, stream);
+    case 1283: return a.a_packed ? launch_sp<128, true, 3>(a, stream) : launch_sp<128, false, 3>(a, stream);
+    case 643: return a.a_packed ? launch_sp<64, true, 3>(a, stream) : launch_sp<64, false, 3>(a, stream);
   }
-  if (bn == 128) return a.a_packed ? launch_sp<128, true, 4>(a, stream) : launch_sp<128, false, 4>(a, stream);
-  if (bn == 64) return a.a_packed ? launch_sp<64, true, 4>(a, stream) : launch_sp<64, false, 4>(a, stream);
-  if (bn == 3128) return a.a_packed ? launch_sp<128, true, 3>(a, stream) : launch_sp<128, false, 3>(a, stream);
-  return a.a_packed ? launch_sp<64, true, 3>(a, stream) : launch_sp<64, false, 3>(a, stream);
+  EVK_REQUIRE(false, EVK_E_INVALID, "conv1x1_sp: no %d-wide tile with %d stages", r.bn, r.stages);
 }
 
 }  // namespace evk

@@ -14,7 +14,7 @@
 // LDS: halo [2 stages][3 planes][10 x 32 slots][32 B] (pitch 32 >= 18 so that the 16-lane groups of a ds_read_b128
 // always cover 16 distinct row residues), weights [2 stages][3 taps][3 planes][128 rows][32 B]; 16-byte halves of a
 // 32-byte row are swapped on odd 8-row groups (conflict-free b128 reads for any tap shift).
-#include "igemm_common.hpp"
+#include "conv_route.hpp"
 #include "split_weight.hpp"
 #include "lds_dma.hpp"
 #include <stdlib.h>
@@ -328,45 +328,13 @@ __global__ __launch_bounds__(256 + 64 * MW) void conv3x3_halo_x3_kernel(const IG
   if (p.out_amax) amax_commit(p.out_amax, amax_l.m);
 }
 
-// does the halo kernel take this launch?  (also decides the layout evk_conv2d_split_weight produces)
-bool conv3x3_halo_applies(const IGemmArgs& a) {
-  static const int on = getenv("EVK_X3_HALO") ? atoi(getenv("EVK_X3_HALO")) : 1;
-  if (!on) return false;
+// 3x3 'same' stride-1 taps in either direction (forward, or stride-1 data gradient: the sign of oys flips the direction);
+// pairs of channels are split together, so Cs must be even: % 8 keeps the 16-byte loads
+bool conv3x3_halo_supports(const IGemmArgs& a) {
   if (a.kh != 3 || a.kw != 3 || a.ash != 1 || a.asw != 1) return false;
   if (!((a.oys == 1 || a.oys == -1) && a.oy0 == -a.oys && (a.oxs == 1 || a.oxs == -1) && a.ox0 == -a.oxs)) return false;
   if (a.Hm != a.Hs || a.Wm != a.Ws) return false;
-  // patches of 8 (or 16) x 16 output pixels; the last row / column of patches may hang over the edge of the map (the halo
-  // loads zeros there, the epilogue drops those rows) as long as at least 3/4 of the patch grid is map
-  // (round 4: H % 8 == 0 and W % 16 == 0 were required until then — a 616 x 344 scene, or the stride-4 map of a 416-wide
-  // tile, fell back to the implicit-GEMM kernels)
-  {
-    const long long cover = (long long)ceil_div(a.Hm, 8) * 8 * ceil_div(a.Wm, kPW) * kPW;
-    if (a.Hm < 4 || a.Wm < 8 || 4LL * a.Hm * a.Wm < 3 * cover) return false;
-  }
-  // (reduction channels: whole 16-channel chunks, or a partial last one as long as three quarters of the chunks' slots are
-  // channels — Cin = 200 = 12.5 chunks; pairs of channels are split together, so Cs must be even: % 8 keeps the 16-byte loads)
-  if ((a.Cs % 8) != 0 || 4 * a.Cs < 3 * ceil_div(a.Cs, kCh) * kCh || a.Cd < 64 || (!a.dense_dst && (a.dsh != 1 || a.dsw != 1))) return false;
-  // enough workgroups for the 256 CUs, if necessary with the 64-wide N tile
-  // (EVK_X3_HALO_MIN_WG=0 makes the choice independent of the batch size: tests/test_linearity_pinned_gpu.py pins the
-  // accumulation order — chunk-major here, tap-major in the implicit-GEMM kernels — for a batch and its halves)
-  static const long long min_wg = getenv("EVK_X3_HALO_MIN_WG") ? atoll(getenv("EVK_X3_HALO_MIN_WG")) : 256;
-  const long long patches = (long long)a.N * ceil_div(a.Hm, 8) * ceil_div(a.Wm, kPW);
-  return patches * ceil_div(a.Cd, 64) >= min_wg;
-}
-
-// the same decision from a convolution descriptor (forward, or stride-1 data gradient)
-bool conv_desc_uses_halo(const evk_conv_desc* d, int for_dgrad) {
-  if (d->stride_h != 1 || d->stride_w != 1 || d->dil_h != 1 || d->dil_w != 1 || d->pad_h != 1 || d->pad_w != 1) return false;
-  IGemmArgs a{};
-  a.N = d->N; a.kh = d->kh; a.kw = d->kw; a.ash = 1; a.asw = 1; a.dense_dst = 1; a.dsh = 1; a.dsw = 1;
-  if (!for_dgrad) {
-    a.Hs = d->H; a.Ws = d->W; a.Cs = d->Cin; a.Hm = d->Ho; a.Wm = d->Wo; a.Cd = d->Cout;
-    a.oy0 = -1; a.oys = 1; a.ox0 = -1; a.oxs = 1;
-  } else {
-    a.Hs = d->Ho; a.Ws = d->Wo; a.Cs = d->Cout; a.Hm = d->H; a.Wm = d->W; a.Cd = d->Cin;
-    a.oy0 = 1; a.oys = -1; a.ox0 = 1; a.oxs = -1;
-  }
-  return conv3x3_halo_applies(a);
+  return (a.Cs % 8) == 0 && (a.dense_dst || (a.dsh == 1 && a.dsw == 1));
 }
 
 template <int BN, int PH, int NPX, bool WDMA = false, int MW = 4>
@@ -402,37 +370,21 @@ static int launch_halo(IGemmArgs& a, hipStream_t stream) {
   return launch_halo_np<BN, PH, 3>(a, stream);
 }
 
-int launch_conv3x3_halo(IGemmArgs& a, hipStream_t stream) {
-  if (!conv3x3_halo_applies(a)) return 1;
-  static const bool tune = getenv("EVK_TUNE") != nullptr;
-  if (tune) {   // tools/autotune_convs.py
-    const char* f = getenv("EVK_X3_HALO_FORCE");
-    if (f && *f) {
-      if (!strcmp(f, "h64x8")) return launch_halo<64, 8>(a, stream);
-      if (!strcmp(f, "m64x8")) return launch_halo<64, 8, 8>(a, stream);
-      if (!strcmp(f, "h64x16")) return launch_halo<64, 16>(a, stream);
-      if (!strcmp(f, "m64x16")) return launch_halo<64, 16, 8>(a, stream);
-      if (!strcmp(f, "h128x8") && a.Cd > 64) return launch_halo<128, 8>(a, stream);
-      if (!strcmp(f, "h128x16") && a.Cd > 64) return launch_halo<128, 16>(a, stream);
-      if (!strcmp(f, "m128x8") && a.Cd > 64) return launch_halo<128, 8, 8>(a, stream);
-      if (!strcmp(f, "m128x16") && a.Cd > 64) return launch_halo<128, 16, 8>(a, stream);
-    }
+int launch_conv3x3_halo(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
+  static_assert(kPW == 16 && kCh == 16, "conv_route.hip counts patches and chunks with these");
+  EVK_REQUIRE(conv3x3_halo_supports(a) && (r.mw == 4 || a.planes == 2), EVK_E_INVALID,
+              "conv3x3_halo: routed a launch it cannot take");
+  switch (r.bn * 1000 + r.ph * 10 + r.mw) {
+    case 64084: return launch_halo<64, 8>(a, stream);
+    case 64088: return launch_halo<64, 8, 8>(a, stream);
+    case 64164: return launch_halo<64, 16>(a, stream);
+    case 64168: return launch_halo<64, 16, 8>(a, stream);
+    case 128084: return launch_halo<128, 8>(a, stream);
+    case 128088: return launch_halo<128, 8, 8>(a, stream);
+    case 128164: return launch_halo<128, 16>(a, stream);
+    case 128168: return launch_halo<128, 16, 8>(a, stream);
   }
-  // workgroup counts from which the 128-wide tile / the 16-row patch is taken (swept in the step in round 5, where the chip is
-  // shared with the side stream: 128 / 384 / 768 all within 0.1 % of 256)
-  constexpr long long min128 = 256, mintall = 256;
-  if (a.Cd <= 64 || (long long)a.N * ceil_div(a.Hm, 8) * ceil_div(a.Wm, kPW) * ceil_div(a.Cd, 128) < min128)
-    return launch_halo<64, 8>(a, stream);   // small maps (16^2 .. 32^2): 64-wide tiles keep every CU busy
-  // 16 x 16 patches (256 GEMM rows) halve the weight bytes per MFMA, the larger share of the staging traffic now;
-  // taken when they still fill the chip.  With the weights fed by DMA (f16x2) the staging waves no longer hold the matrix
-  // waves back, and eight matrix waves (two per SIMD) are 1-7 % ahead of four on every 128-wide shape
-  // (tools/autotune_convs.py: 777 -> 763 us on 3x3x256 @128^2, 61 -> 57 on 3x3x128 @64^2, 59-62 -> 58 on 3x3x256 @32^2).
-  const bool wide8 = a.planes == 2;
-  // (16-row patches unless they would add a mostly empty last patch row: H % 16 in 1..8 is served better by 8-row patches)
-  const bool tall_fits = (a.Hm % 16) == 0 || (a.Hm % 16) > 8;
-  if (tall_fits && (long long)a.N * ceil_div(a.Hm, 16) * ceil_div(a.Wm, kPW) * ceil_div(a.Cd, 128) >= mintall)
-    return wide8 ? launch_halo<128, 16, 8>(a, stream) : launch_halo<128, 16>(a, stream);
-  return wide8 ? launch_halo<128, 8, 8>(a, stream) : launch_halo<128, 8>(a, stream);
+  EVK_REQUIRE(false, EVK_E_INVALID, "conv3x3_halo: no %d-wide tile on %d-row patches with %d matrix waves", r.bn, r.ph, r.mw);
 }
 
 // planes for the halo kernel: out[pt][tap][chunk][row][16] bf16; tap = jy*3 + jx in the kernel's (affine) tap

@@ -18,13 +18,12 @@
 // direct kernel's.  K order: chunk of 16 channels, kernel row, xi.  Values differ from the direct kernels' by rounding
 // (tests/test_wino_gpu.py: both ~2e-6 from fp64).
 //
-// Workgroup: PH x 16 output pixels (= PH x 8 pairs = GEMM rows) x BN channels, eight SYMMETRIC waves (4 along M x 2 along N; the
-// 128 accumulator registers of a 32-pair x 64-channel x 4-xi wave tile leave room for two waves per SIMD and no more, so
-// there are no staging waves): every wave issues a quarter of an iteration's weight DMA (pre-transformed, pre-split
-// planes [plane][ky][xi][chunk][Cout][16], `buffer_load ... lds`, two stages), and once per chunk transforms one item of
-// the NEXT chunk's halo — 4 pixels x 4 channels from global memory into the four xi images — between the MFMAs of the
-// current one.  LDS: image [2 stages][2 planes][4 xi][PH + 2 rows][8 pairs][32 B] + weights [2 stages][4 xi][2 planes][BN][32 B].
-#include "igemm_common.hpp"
+// Workgroup: PH x 16 output pixels (= PH x 8 pairs = GEMM rows) x BN channels, eight matrix waves (4 along M x 2 along N, two per
+// SIMD: 128 accumulator registers of a 32-pair x 64-channel x 4-xi wave tile) and four staging waves (see the kernel's own
+// comment below).  The staging waves issue each iteration's weight DMA (pre-transformed, pre-split planes
+// [plane][ky][xi][chunk][Cout][16], `buffer_load ... lds`, two stages) and once per chunk transform the NEXT chunk's halo —
+// items of 4 pixels x 4 channels from global memory into the four xi images — while the matrix waves multiply the current one.  LDS: image [2 stages][2 planes][4 xi][PH + 2 rows][8 pairs][32 B] + weights [2 stages][4 xi][2 planes][BN][32 B].
+#include "conv_route.hpp"
 #include "split_weight.hpp"
 #include "lds_dma.hpp"
 #include <stdlib.h>
@@ -282,45 +281,10 @@ __global__ __launch_bounds__(768) void conv3x3_wino_x3_kernel(const IGemmArgs p,
   if (p.out_amax) amax_commit(p.out_amax, amax_l.m);
 }
 
-// EVK_WINO: 0 = never (the direct halo kernel everywhere), 1 = where measured ahead (default), 2 = wherever it applies (tests)
-static int wino_mode() {
-  static const int m = getenv("EVK_WINO") ? atoi(getenv("EVK_WINO")) : 1;
-  return m;
-}
-
-// geometry part of the decision — a pure function of the launch shape, shared with the weight-plane producers
-static bool wino_geometry(int N, int Hm, int Wm, int Cs, int Cd) {
-  const int mode = wino_mode();
-  if (!mode) return false;
-  if (Hm < 8 || Wm < 8 || (Cs % 8) != 0 || Cd < 64) return false;
-  if (4 * Cs < 3 * ceil_div(Cs, kWCh) * kWCh) return false;
-  const long long cover = (long long)ceil_div(Hm, 16) * 16 * ceil_div(Wm, kWPW) * kWPW;
-  if (4LL * Hm * Wm < 3 * cover) return false;
-  if (mode >= 2) return true;
-  // one 16 x 16 patch x 128 channels per workgroup: whole 128-wide column tiles and at least one workgroup per CU (measured,
-  // tools/wino_probe.py, us direct -> this: 3x3x256 @128^2 926 -> 815 forward / 802 -> 707 data gradient, 256 -> 128 477 -> 430,
-  // 256 @64^2 212 -> 190, 128 @64^2 57 -> 52; behind on 64 -> 64 @128^2 (half of the column tile is padding: 73 -> 103) and on
-  // the 32^2 / 16^2 maps, which are not bound by the matrix pipe)
-  return (Cd % 128) == 0 && (long long)N * ceil_div(Hm, 16) * ceil_div(Wm, kWPW) * (Cd / 128) >= 256;
-}
-
-bool conv3x3_wino_applies(const IGemmArgs& a) {
-  if (a.planes != 2 || a.kh != 3 || a.kw != 3 || a.ash != 1 || a.asw != 1) return false;
-  if (!((a.oys == 1 || a.oys == -1) && a.oy0 == -a.oys && (a.oxs == 1 || a.oxs == -1) && a.ox0 == -a.oxs)) return false;
-  if (a.Hm != a.Hs || a.Wm != a.Ws || (!a.dense_dst && (a.dsh != 1 || a.dsw != 1))) return false;
-  if ((long long)a.N * a.Hs * a.Ws * a.Cs * 4 >= 0x7fffffffLL) return false;   // (the halo is loaded through a buffer descriptor)
-  // (only where the halo kernel applies as well: the weight-plane producers of the other arithmetics lay those shapes out
-  // for it, and a multi-tensor split job is built before the arithmetic is known)
-  return conv3x3_halo_applies(a) && wino_geometry(a.N, a.Hm, a.Wm, a.Cs, a.Cd);
-}
-
-// the same decision from a convolution descriptor (forward, or stride-1 data gradient) — f16x2 arithmetic only, which the
-// caller knows (the weight-plane producers: a scale word is present)
-bool conv_desc_uses_wino(const evk_conv_desc* d, int for_dgrad) {
-  if (d->kh != 3 || d->kw != 3) return false;
-  if (d->stride_h != 1 || d->stride_w != 1 || d->dil_h != 1 || d->dil_w != 1 || d->pad_h != 1 || d->pad_w != 1) return false;
-  if (!conv_desc_uses_halo(d, for_dgrad)) return false;
-  return for_dgrad ? wino_geometry(d->N, d->H, d->W, d->Cout, d->Cin) : wino_geometry(d->N, d->Ho, d->Wo, d->Cin, d->Cout);
+// f16x2 arithmetic; the geometry the halo kernel takes; the halo is loaded through a buffer descriptor (32-bit byte offsets)
+bool conv3x3_wino_supports(const IGemmArgs& a) {
+  if (a.planes != 2 || !conv3x3_halo_supports(a)) return false;
+  return (long long)a.N * a.Hs * a.Ws * a.Cs * 4 < 0x7fffffffLL;
 }
 
 template <int BN, int PH, bool PK>
@@ -339,8 +303,9 @@ static int launch_wino_t(IGemmArgs& a, hipStream_t stream) {
   return check_launch("conv3x3_wino_x3");
 }
 
-int launch_conv3x3_wino(IGemmArgs& a, hipStream_t stream) {
-  if (!conv3x3_wino_applies(a)) return 1;
+int launch_conv3x3_wino(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
+  static_assert(kWPW == 16 && kWCh == 16, "conv_route.hip counts patches and chunks with these");
+  EVK_REQUIRE(conv3x3_wino_supports(a) && r.bn == 128 && r.ph == 16, EVK_E_INVALID, "conv3x3_wino: routed a launch it cannot take");
   return a.a_packed ? launch_wino_t<128, 16, true>(a, stream) : launch_wino_t<128, 16, false>(a, stream);
 }
 

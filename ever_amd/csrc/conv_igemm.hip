@@ -28,7 +28,7 @@
 // The gather is branch-free: every 16-byte load is issued from a clamped (valid) 32-bit element
 // offset and the zero fill is applied when the chunk is written to LDS, after the MFMA block, so the
 // prefetch stays in flight under the MFMAs.
-#include "igemm_common.hpp"
+#include "conv_route.hpp"
 
 namespace evk {
 
@@ -276,31 +276,37 @@ __global__ __launch_bounds__(256) void conv1x1_smallm_kernel(const float* __rest
   }
 }
 
-int launch_igemm(IGemmArgs& a, hipStream_t stream) {
+static int check_fp32_sizes(const IGemmArgs& a) {
   const long long src_elems = (long long)a.N * a.Hs * a.Ws * a.Cs;
   const long long wgt_elems = (long long)a.Cd * a.Ktot;
-  if (src_elems >= 0x7fffffffLL || wgt_elems >= 0x7fffffffLL) {
-    set_error("conv_igemm: tensors of 2^31 or more elements are not supported (%lld / %lld)", src_elems, wgt_elems);
-    return EVK_E_UNSUPPORTED;
+  EVK_REQUIRE(src_elems < 0x7fffffffLL && wgt_elems < 0x7fffffffLL, EVK_E_UNSUPPORTED,
+              "conv_igemm: tensors of 2^31 or more elements are not supported (%lld / %lld)", src_elems, wgt_elems);
+  return EVK_OK;
+}
+
+bool conv1x1_smallm_supports(const IGemmArgs& a) {
+  return a.kh == 1 && a.kw == 1 && a.M <= kSmallM && a.dense_dst && !a.accum && a.ash == 1 && a.asw == 1 && a.oy0 == 0 &&
+         a.ox0 == 0 && a.Hm == a.Hs && a.Wm == a.Ws;
+}
+
+int launch_conv1x1_smallm(IGemmArgs& a, const ConvRoute&, hipStream_t stream) {
+  if (int rc = check_fp32_sizes(a)) return rc;
+  EVK_REQUIRE(conv1x1_smallm_supports(a), EVK_E_INVALID, "conv1x1_smallm: routed a launch it cannot take");
+  hipLaunchKernelGGL(conv1x1_smallm_kernel, dim3(a.Cd), dim3(256), 0, stream, a.src, a.wgt, a.bias, a.dst, a.M, a.Ktot, a.Cd,
+                     a.relu);
+  return check_launch("conv1x1_smallm");
+}
+
+int launch_igemm(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
+  if (int rc = check_fp32_sizes(a)) return rc;
+  switch (r.bm * 1000 + r.bn) {
+    case 256064: return launch_cfg<256, 64, 4, 1>(a, stream);
+    case 128064: return launch_cfg<128, 64, 2, 2>(a, stream);
+    case 64064: return launch_cfg<64, 64, 2, 2>(a, stream);
+    case 128128: return launch_cfg<128, 128, 2, 2>(a, stream);
+    case 64128: return launch_cfg<64, 128, 2, 2>(a, stream);
   }
-  if (a.kh == 1 && a.kw == 1 && a.M <= kSmallM && a.dense_dst && !a.accum && a.ash == 1 && a.asw == 1 && a.oy0 == 0 &&
-      a.ox0 == 0 && a.Hm == a.Hs && a.Wm == a.Ws) {
-    hipLaunchKernelGGL(conv1x1_smallm_kernel, dim3(a.Cd), dim3(256), 0, stream, a.src, a.wgt, a.bias, a.dst, a.M,
-                       a.Ktot, a.Cd, a.relu);
-    return check_launch("conv1x1_smallm");
-  }
-  // Tile choice: N tile 64 for narrow outputs, else 128; M tile as large as keeps >= 2 workgroups
-  // per CU (256 CUs) in flight.
-  const int bn = (a.Cd <= 64) ? 64 : 128;
-  const long long tn = ceil_div(a.Cd, bn);
-  auto tiles = [&](int bm) { return (long long)ceil_div(a.M, bm) * tn; };
-  if (bn == 64) {
-    if (tiles(256) >= 512) return launch_cfg<256, 64, 4, 1>(a, stream);
-    if (tiles(128) >= 512) return launch_cfg<128, 64, 2, 2>(a, stream);
-    return launch_cfg<64, 64, 2, 2>(a, stream);
-  }
-  if (tiles(128) >= 512) return launch_cfg<128, 128, 2, 2>(a, stream);
-  return launch_cfg<64, 128, 2, 2>(a, stream);
+  EVK_REQUIRE(false, EVK_E_INVALID, "conv_igemm: no %d x %d tile", r.bm, r.bn);
 }
 
 static int check_desc(const evk_conv_desc* d) {
@@ -342,7 +348,28 @@ AxisPlan plan_axis(int c, int pad, int dil, int stride, int ksize) {
 
 using namespace evk;
 
-static inline int kpad32(int k) { return (k + 31) & ~31; }
+// every forward / data-gradient launch: the planner names kernel and tile, the kernel's launcher does the rest
+static int route_and_launch(IGemmArgs& a, hipStream_t stream) {
+  const RouteKnobs knobs = route_knobs();
+  ConvRoute r = route_conv(a, a.wgt3 != nullptr, knobs, kAnyDevice);
+  if (r.kernel == ConvKernel::C1Ps2) {   // the one route that depends on the device: asked only then (a runtime call per launch)
+    const int cus_per_xcd = device_cus_per_xcd();
+    EVK_REQUIRE(cus_per_xcd > 0, EVK_E_LAUNCH, "conv: cannot query the device");
+    r = route_conv(a, true, knobs, cus_per_xcd);
+  }
+  switch (r.kernel) {
+    case ConvKernel::Igemm: return launch_igemm(a, r, stream);
+    case ConvKernel::SmallM: return launch_conv1x1_smallm(a, r, stream);
+    case ConvKernel::Wino: return launch_conv3x3_wino(a, r, stream);
+    case ConvKernel::Halo: return launch_conv3x3_halo(a, r, stream);
+    case ConvKernel::C1Ps2: return launch_conv1x1_ps2(a, r, stream);
+    case ConvKernel::C1Dma: return launch_conv1x1_dma(a, r, stream);
+    case ConvKernel::C1Sp: return launch_conv1x1_sp(a, r, stream);
+    case ConvKernel::X3Ws: return launch_igemm_x3ws(a, r, stream);
+    case ConvKernel::X3: return launch_igemm_x3(a, r, stream);
+  }
+  EVK_REQUIRE(false, EVK_E_INVALID, "conv: unknown route");
+}
 
 // w3 != nullptr selects the bf16-split kernel (conv_igemm_x3.hip) on pre-split weight planes
 static int conv_fwd_any(const evk_conv_desc* d, const float* x, const float* w, const uint16_t* w3, const float* bias,
@@ -352,19 +379,10 @@ static int conv_fwd_any(const evk_conv_desc* d, const float* x, const float* w, 
   int rc = check_desc(d);
   if (rc) return rc;
   EVK_REQUIRE(x && (w || w3) && y, EVK_E_INVALID, "conv2d_fwd: null pointer");
-  IGemmArgs a{};
   EVK_REQUIRE(residual != y, EVK_E_INVALID, "conv2d_fwd: residual must not alias y");
+  IGemmArgs a = igemm_geometry_fwd(d);
   a.src = x; a.wgt = w; a.wgt3 = w3; a.bias = bias; a.accum = residual; a.dst = y;
-  a.N = d->N; a.Hs = d->H; a.Ws = d->W; a.Cs = d->Cin;
-  a.Hm = d->Ho; a.Wm = d->Wo; a.Cd = d->Cout;
-  a.kh = d->kh; a.kw = d->kw; a.cpt = d->Cin / 4;
-  a.ash = d->stride_h; a.asw = d->stride_w;
-  a.oy0 = -d->pad_h; a.oys = d->dil_h; a.ox0 = -d->pad_w; a.oxs = d->dil_w;
-  a.M = d->N * d->Ho * d->Wo;
-  a.Ktot = d->kh * d->kw * d->Cin;
-  a.Hd = d->Ho; a.Wd = d->Wo; a.dsh = 1; a.dsw = 1; a.dense_dst = 1;
   a.relu = (flags & EVK_CONV_RELU) ? 1 : 0;
-  a.Kpad = kpad32(a.Ktot);
   a.planes = planes;
   a.a_scale = a_scale; a.w_scale = w_scale;
   a.a_packed = (planes == 2 && (flags & EVK_CONV_X_PACKED)) ? 1 : 0;
@@ -373,17 +391,9 @@ static int conv_fwd_any(const evk_conv_desc* d, const float* x, const float* w, 
   a.bn_buf = bn_parts;
   a.bn_cap = bn_cap;
   if (nparts) *nparts = 0;
-  if (w3) {
-    int hr = launch_conv3x3_wino(a, (hipStream_t)stream);         // 3x3 'same', f16x2, large maps: Winograd F(2,3) along x
-    if (hr == 1) hr = launch_conv3x3_halo(a, (hipStream_t)stream);   // 3x3 'same' convolutions: LDS-halo kernel
-    if (hr != 1) {
-      if (nparts && hr == EVK_OK) *nparts = a.bn_parts;
-      return hr;
-    }
-  }
-  const int rc2 = w3 ? launch_igemm_x3(a, (hipStream_t)stream) : launch_igemm(a, (hipStream_t)stream);
-  if (nparts && rc2 == EVK_OK) *nparts = a.bn_parts;
-  return rc2;
+  rc = route_and_launch(a, (hipStream_t)stream);
+  if (nparts && rc == EVK_OK) *nparts = a.bn_parts;
+  return rc;
 }
 
 extern "C" int evk_conv2d_fwd(const evk_conv_desc* d, const float* x, const float* w, const float* bias,
@@ -472,38 +482,20 @@ static int conv_dgrad_any(const evk_conv_desc* d, const float* dy, const float* 
   size_t woff3 = 0;  // ... and the class planes by evk_conv2d_split_weight(for_dgrad = 1)
   for (int cy = 0; cy < sh; ++cy)
     for (int cx = 0; cx < sw; ++cx) {
-      const AxisPlan py = plan_axis(cy, d->pad_h, d->dil_h, sh, d->kh);
-      const AxisPlan px = plan_axis(cx, d->pad_w, d->dil_w, sw, d->kw);
-      const int Hm = d->H > cy ? (d->H - cy + sh - 1) / sh : 0;
-      const int Wm = d->W > cx ? (d->W - cx + sw - 1) / sw : 0;
-      const size_t wsize = (size_t)d->Cin * py.nt * px.nt * d->Cout;
-      if (py.nt > 0 && px.nt > 0 && Hm > 0 && Wm > 0) {
-        IGemmArgs a{};
+      IGemmArgs a = igemm_geometry_dgrad(d, cy, cx);
+      if (a.kh > 0 && a.kw > 0 && a.Hm > 0 && a.Wm > 0) {
         a.planes = planes;
         a.a_scale = a_scale; a.w_scale = w_scale;
         a.a_packed = dy_packed;
         a.out_amax = out_amax;
         a.src = dy; a.wgt = wt ? wt + woff : nullptr; a.wgt3 = wt3 ? wt3 + woff3 : nullptr;
-        a.bias = nullptr; a.accum = accum; a.dst = dx;
+        a.accum = accum; a.dst = dx;
         a.accum_bits = accum_bits;
-        a.N = d->N; a.Hs = d->Ho; a.Ws = d->Wo; a.Cs = d->Cout;
-        a.Hm = Hm; a.Wm = Wm; a.Cd = d->Cin;
-        a.kh = py.nt; a.kw = px.nt; a.cpt = d->Cout / 4;
-        a.ash = 1; a.asw = 1;
-        a.oy0 = py.o0; a.oys = py.ostep; a.ox0 = px.o0; a.oxs = px.ostep;
-        a.M = d->N * Hm * Wm;
-        a.Ktot = py.nt * px.nt * d->Cout;
-        a.Hd = d->H; a.Wd = d->W; a.dsh = sh; a.dsw = sw; a.doy = cy; a.dox = cx;
-        a.dense_dst = (sh == 1 && sw == 1) ? 1 : 0;
-        a.relu = 0;
-        a.Kpad = kpad32(a.Ktot);
-        rc = wt3 ? launch_conv3x3_wino(a, st) : 1;
-        if (rc == 1) rc = wt3 ? launch_conv3x3_halo(a, st) : 1;
-        if (rc == 1) rc = wt3 ? launch_igemm_x3(a, st) : launch_igemm(a, st);
+        rc = route_and_launch(a, st);
         if (rc) return rc;
       }
-      woff += wsize;
-      woff3 += (size_t)3 * d->Cin * kpad32(py.nt * px.nt * d->Cout);
+      woff += (size_t)d->Cin * a.Ktot;
+      woff3 += (size_t)3 * d->Cin * a.Kpad;
     }
   return EVK_OK;
 }

@@ -16,7 +16,7 @@
 // LDS stage: 3 x [BM][32] + 3 x [BN][32] bf16, rows of 64 bytes, 16-byte chunk index ^= (row>>2)&3 so
 // that the ds_read_b128 fragment reads of a 16-lane group cover 16 distinct 16-byte slots.
 // Fragment: lane l holds row l&31, k = 16*kk + 8*(l>>5) .. +7 (one ds_read_b128) for A and B alike.
-#include "igemm_common.hpp"
+#include "conv_route.hpp"
 #include "split_weight.hpp"
 #include <stdlib.h>
 #include <string.h>
@@ -271,61 +271,23 @@ static int launch_cfg3(IGemmArgs& a, hipStream_t stream) {
   return launch_cfg3_np<BM, BN, WAVES_M, WAVES_N, NBUF, 3>(a, stream);
 }
 
-int launch_igemm_x3(IGemmArgs& a, hipStream_t stream) {
+// the register-staged split kernels (this one and conv_igemm_x3ws.hip): 32-bit element offsets, 16-byte loads of 8 channels
+bool igemm_x3_supports(const IGemmArgs& a) {
   const long long src_elems = (long long)a.N * a.Hs * a.Ws * a.Cs;
   const long long wgt_elems = (long long)a.Cd * a.Kpad * 3;
-  if (src_elems >= 0x7fffffffLL || wgt_elems >= 0x7fffffffLL) {
-    set_error("conv_igemm_x3: tensors of 2^31 or more elements are not supported");
-    return EVK_E_UNSUPPORTED;
+  return src_elems < 0x7fffffffLL && wgt_elems < 0x7fffffffLL && (a.Cs & 7) == 0;
+}
+
+int launch_igemm_x3(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
+  EVK_REQUIRE((a.Cs & 7) == 0, EVK_E_UNSUPPORTED, "conv_igemm_x3: source channels (%d) must be a multiple of 8", a.Cs);
+  EVK_REQUIRE(igemm_x3_supports(a), EVK_E_UNSUPPORTED, "conv_igemm_x3: tensors of 2^31 or more elements are not supported");
+  switch (r.bm * 1000 + r.bn) {
+    case 128128: return launch_cfg3<128, 128, 2, 2, 1>(a, stream);
+    case 64128: return launch_cfg3<64, 128, 2, 2, 1>(a, stream);
+    case 128064: return launch_cfg3<128, 64, 2, 2, 1>(a, stream);
+    case 64064: return launch_cfg3<64, 64, 2, 2, 1>(a, stream);
   }
-  if ((a.Cs & 7) != 0) {
-    set_error("conv_igemm_x3: source channels (%d) must be a multiple of 8", a.Cs);
-    return EVK_E_UNSUPPORTED;
-  }
-  static const bool tune = getenv("EVK_TUNE") != nullptr;
-  if (tune) {   // tools/autotune_convs.py: EVK_X3_FORCE names the tile shape (read on every launch)
-    const char* f = getenv("EVK_X3_FORCE");
-    if (f && *f) {
-      if (!strcmp(f, "w256")) return launch_igemm_x3ws_forced(a, 256, stream);
-      if (!strcmp(f, "w128")) return launch_igemm_x3ws_forced(a, 128, stream);
-      if (!strcmp(f, "w64")) return launch_igemm_x3ws_forced(a, 64, stream);
-      if (!strcmp(f, "d256") && conv1x1_dma_applicable(a)) return launch_conv1x1_dma_forced(a, 256, stream);
-      if (!strcmp(f, "d128") && conv1x1_dma_applicable(a)) return launch_conv1x1_dma_forced(a, 128, stream);
-      if (!strcmp(f, "d64") && conv1x1_dma_applicable(a)) return launch_conv1x1_dma_forced(a, 64, stream);
-      if (!strcmp(f, "e128") && conv1x1_dma_applicable(a)) return launch_conv1x1_dma_forced(a, 2128, stream);
-      if (!strcmp(f, "e64") && conv1x1_dma_applicable(a)) return launch_conv1x1_dma_forced(a, 2064, stream);
-      if (!strcmp(f, "q128") && conv1x1_ps2_applicable(a)) return launch_conv1x1_ps2(a, stream);
-      if (!strcmp(f, "s128") && conv1x1_sp_applicable(a)) return launch_conv1x1_sp_forced(a, 128, stream);
-      if (!strcmp(f, "s64") && conv1x1_sp_applicable(a)) return launch_conv1x1_sp_forced(a, 64, stream);
-      if (!strcmp(f, "t128") && conv1x1_sp_applicable(a)) return launch_conv1x1_sp_forced(a, 3128, stream);
-      if (!strcmp(f, "t64") && conv1x1_sp_applicable(a)) return launch_conv1x1_sp_forced(a, 3064, stream);
-      if (!strcmp(f, "c128x128")) return launch_cfg3<128, 128, 2, 2, 1>(a, stream);
-      if (!strcmp(f, "c64x128")) return launch_cfg3<64, 128, 2, 2, 1>(a, stream);
-      if (!strcmp(f, "c128x64")) return launch_cfg3<128, 64, 2, 2, 1>(a, stream);
-      if (!strcmp(f, "c64x64")) return launch_cfg3<64, 64, 2, 2, 1>(a, stream);
-    }
-  }
-  {
-    const int rc = launch_conv1x1_dma(a, stream);  // both operands by LDS-DMA: the one-tap layers of the f16x2 arithmetic
-    if (rc != 1) return rc;
-  }
-  {
-    const int rc = launch_igemm_x3ws(a, stream);  // wave-specialised form for the large layers
-    if (rc != 1) return rc;
-  }
-  const int bn = (a.Cd <= 64) ? 64 : 128;
-  const long long tn = ceil_div(a.Cd, bn);
-  auto tiles = [&](int bm) { return (long long)ceil_div(a.M, bm) * tn; };
-  // single LDS stage (48 KB at 128x128 => 2-3 workgroups per CU, whose split / MFMA phases interleave)
-  // measured faster than a double-buffered stage at 1 workgroup per CU: 180 vs 157 TFLOP/s on 3x3x256 @128^2
-  if (bn == 64) {
-    if (tiles(128) >= 256) return launch_cfg3<128, 64, 2, 2, 1>(a, stream);
-    return launch_cfg3<64, 64, 2, 2, 1>(a, stream);
-  }
-  if (tiles(128) >= 256) return launch_cfg3<128, 128, 2, 2, 1>(a, stream);
-  if (tiles(64) >= 256) return launch_cfg3<64, 128, 2, 2, 1>(a, stream);
-  // 16^2 maps (M = 4096 rows at batch 16): 64 x 64 tiles are the only ones that give every CU a workgroup
-  return launch_cfg3<64, 64, 2, 2, 1>(a, stream);
+  EVK_REQUIRE(false, EVK_E_INVALID, "conv_igemm_x3: no %d x %d tile", r.bm, r.bn);
 }
 
 // Weight planes for the split kernel.  Forward (`classes == nullptr` form): row co, k = (ky, kx, ci) as in
@@ -344,8 +306,6 @@ __global__ void split_weight_dgrad_kernel(const float* __restrict__ w, uint16_t*
   split_dgrad_body(w, out, Cout, kh, kw, Cin, ky0, ksy, nty, kx0, ksx, ntx, Kpad,
                    (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, wscale);
 }
-
-static inline int kpad32(int k) { return (k + 31) & ~31; }
 
 }  // namespace evk
 
@@ -382,13 +342,12 @@ static int split_weight_any(const evk_conv_desc* d, const float* w, int32_t for_
               "split_weight: bad stride/dilation");
   hipStream_t st = (hipStream_t)stream;
   uint16_t* out = reinterpret_cast<uint16_t*>(wsplit);
-  // 3x3 'same' convolutions served by the LDS-halo kernel take their planes in that kernel's own order (the
-  // decision is a pure function of the descriptor, so the consumer makes the same one); never larger than the
-  // generic layout.
-  if (wscale && conv_desc_uses_wino(d, for_dgrad ? 1 : 0))   // (12 x 2 planes of taps: inside the 9 x 3 the buffer is sized for)
-    return launch_split_weight_wino(w, out, d->Cout, d->Cin, for_dgrad ? 1 : 0, st, wscale);
-  if (d->kh == 3 && d->kw == 3 && conv_desc_uses_halo(d, for_dgrad ? 1 : 0))
-    return launch_split_weight_halo(w, out, d->Cout, d->Cin, for_dgrad ? 1 : 0, st, wscale);
+  // the 3x3 kernels take their planes in their own order: the planner's stage 1 on the same geometry the consumer will build
+  // (conv_route.hpp), so the two cannot disagree; never larger than the generic layout
+  // (Winograd: 12 x 2 planes of taps, inside the 9 x 3 the buffer is sized for)
+  const PlaneLayout layout = desc_layout(d, for_dgrad ? 1 : 0, wscale ? 2 : 3);
+  if (layout == PlaneLayout::Wino) return launch_split_weight_wino(w, out, d->Cout, d->Cin, for_dgrad ? 1 : 0, st, wscale);
+  if (layout == PlaneLayout::Halo) return launch_split_weight_halo(w, out, d->Cout, d->Cin, for_dgrad ? 1 : 0, st, wscale);
   if (!for_dgrad) {
     const int K = d->kh * d->kw * d->Cin, Kp = kpad32(K);
     const size_t total = (size_t)d->Cout * (Kp >> 1);

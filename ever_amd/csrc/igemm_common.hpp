@@ -338,22 +338,8 @@ inline void bn_stats_setup(IGemmArgs& a, int BM, int BN, int WAVES_M, long long 
   a.bn_parts = (int)parts;
 }
 
-int launch_igemm(IGemmArgs& a, hipStream_t stream);
-int launch_igemm_x3(IGemmArgs& a, hipStream_t stream);
-int launch_igemm_x3ws(IGemmArgs& a, hipStream_t stream);  // 1 = not applicable
-int launch_igemm_x3ws_forced(IGemmArgs& a, int bn, hipStream_t stream);
-int launch_conv1x1_dma(IGemmArgs& a, hipStream_t stream);  // 1 = not applicable (conv1x1_dma.hip)
-int launch_conv1x1_dma_forced(IGemmArgs& a, int bn, hipStream_t stream);
-bool conv1x1_dma_applicable(const IGemmArgs& a);
-int launch_conv1x1_sp_forced(IGemmArgs& a, int bn, hipStream_t stream);   // software-pipelined, loader waves (conv1x1_sp.hip)
-bool conv1x1_sp_applicable(const IGemmArgs& a);
-int launch_conv1x1_ps2(IGemmArgs& a, hipStream_t stream);  // persistent, loader + compute + store waves (conv1x1_ps2.hip)
-bool conv1x1_ps2_applicable(const IGemmArgs& a);
-int launch_conv3x3_halo(IGemmArgs& a, hipStream_t stream);  // 1 = not applicable
-bool conv_desc_uses_halo(const evk_conv_desc* d, int for_dgrad);
-bool conv3x3_halo_applies(const IGemmArgs& a);
-int launch_conv3x3_wino(IGemmArgs& a, hipStream_t stream);  // 1 = not applicable (conv3x3_wino_x3.hip; f16x2 only)
-bool conv_desc_uses_wino(const evk_conv_desc* d, int for_dgrad);   // geometry only: the caller knows the arithmetic
+inline int kpad32(int k) { return (k + 31) & ~31; }   // K of a weight-plane row: whole 32-element steps, zero padded
+
 int launch_split_weight_wino(const float* w, uint16_t* out, int Cout, int Cin, int for_dgrad, hipStream_t st,
                              const uint32_t* wscale);
 int launch_split_weight_halo(const float* w, uint16_t* out, int Cout, int Cin, int for_dgrad, hipStream_t st,

@@ -5,7 +5,7 @@
 // for that job, ~evk_split_job_pairs / 2048, and a (job, block-in-job) map with one row per workgroup), keeps both
 // in device memory and calls evk_conv2d_split_multi after each weight update.
 #include "split_weight.hpp"
-#include "igemm_common.hpp"
+#include "conv_route.hpp"
 
 namespace evk {
 
@@ -26,13 +26,11 @@ __global__ __launch_bounds__(256) void split_weight_multi_kernel(const evk_split
   else if (j.kind == kSplitDgrad)
     split_dgrad_body(w, out, j.arg[0], j.arg[1], j.arg[2], j.arg[3], j.arg[4], j.arg[5], j.arg[6], j.arg[7], j.arg[8],
                      j.arg[9], j.arg[10], t0, nt, wscale);
-  else if (wscale && j.arg[3])   // f16x2 and a shape the Winograd kernel takes (conv_desc_uses_wino)
+  else if (wscale && j.arg[3])   // f16x2 and a shape the Winograd kernel takes (conv_route.hpp: stage 1 under planes = 2)
     split_wino_body(w, out, j.arg[0], j.arg[1], j.arg[2], t0, nt, wscale);
   else
     split_halo_body(w, out, j.arg[0], j.arg[1], j.arg[2], t0, nt, wscale);
 }
-
-static inline int kpad32(int k) { return (k + 31) & ~31; }
 
 }  // namespace evk
 
@@ -40,7 +38,7 @@ using namespace evk;
 
 extern "C" int32_t evk_conv2d_split_job_count(const evk_conv_desc* d, int32_t for_dgrad) {
   if (!d || d->stride_h <= 0 || d->stride_w <= 0) return 0;
-  if (d->kh == 3 && d->kw == 3 && conv_desc_uses_halo(d, for_dgrad ? 1 : 0)) return 1;
+  if (desc_layout(d, for_dgrad ? 1 : 0, 3) != PlaneLayout::Generic) return 1;
   return for_dgrad ? d->stride_h * d->stride_w : 1;
 }
 
@@ -58,11 +56,12 @@ extern "C" int evk_conv2d_split_jobs(const evk_conv_desc* d, const float* w, int
     for (int i = 0; i < 13; ++i) j.arg[i] = 0;
     return j;
   };
-  // the same layout decisions as evk_conv2d_split_weight (the consumer kernels make them from the descriptor too)
-  if (d->kh == 3 && d->kw == 3 && conv_desc_uses_halo(d, for_dgrad ? 1 : 0)) {
+  // the layout the planner's stage 1 names (conv_route.hpp) — the one evk_conv2d_split_weight produces and the launch reads.
+  // The job is built before the arithmetic is known: arg[3] = "the Winograd layout if the planes turn out to be f16x2"
+  if (desc_layout(d, for_dgrad ? 1 : 0, 3) != PlaneLayout::Generic) {
     evk_split_job& j = put(kSplitHalo, out);
     j.arg[0] = d->Cout; j.arg[1] = d->Cin; j.arg[2] = for_dgrad ? 1 : 0;
-    j.arg[3] = conv_desc_uses_wino(d, for_dgrad ? 1 : 0) ? 1 : 0;
+    j.arg[3] = desc_layout(d, for_dgrad ? 1 : 0, 2) == PlaneLayout::Wino ? 1 : 0;
     return n;
   }
   if (!for_dgrad) {

@@ -115,6 +115,15 @@ int32_t evk_conv2d_split_job_count(const evk_conv_desc* d, int32_t for_dgrad);
 int evk_conv2d_split_jobs(const evk_conv_desc* d, const float* w, int32_t for_dgrad, void* wsplit,
                           evk_split_job* jobs /* host */, int32_t max_jobs);
 int64_t evk_split_job_pairs(const evk_split_job* job /* host */);
+/* Host only (no launch, no device needed): which kernel a forward (cls < 0) or data-gradient residue class
+ * (cls = cy * stride_w + cx) launch of this descriptor takes.  planes: 0 the fp32 kernels, 3 bf16x3, 1 bf16, 2 f16x2; flags:
+ * EVK_CONV_X_PACKED (forward) / EVK_CONV_DY_PACKED (data gradient); with_accum: a residual / accumulate operand; with_stats:
+ * the BatchNorm statistics epilogue is requested; cus_per_xcd: compute units per XCD of the device that will run it (32 on
+ * a 256-CU MI355X).  Writes "kernel<template arguments>" as a kernel trace spells the instantiation (empty: the class has
+ * no launch) and, if layout is not NULL, the weight-plane layout that kernel reads — 0 generic, 1 LDS-halo 3x3, 2 Winograd
+ * F(2,3) — which is the layout evk_conv2d_split_weight* / evk_conv2d_split_jobs produce for the same descriptor. */
+int evk_conv2d_route(const evk_conv_desc* d, int32_t cls, int32_t planes, uint32_t flags, int32_t with_accum,
+                     int32_t with_stats, int32_t cus_per_xcd, char* buf, size_t buf_bytes, int32_t* layout);
 int evk_conv2d_split_multi(const evk_split_job* jobs_dev, const int32_t* block_map_dev, int32_t nblocks,
                            void* stream);
 int evk_conv2d_fwd_x3(const evk_conv_desc* d, const float* x, const void* wsplit, const float* bias,

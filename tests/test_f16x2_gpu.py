@@ -292,3 +292,41 @@ def test_scales_from_nearest_add_and_mean4(cuda):
             assert F.absmax_value(hit[2]) == _bits(t)
     finally:
         F.set_conv_math(prev)
+
+
+def test_conv_3x3_on_an_input_of_2_gib(cuda):
+    """1 x 256 x 1450 x 1450 (2.15 GB of activations): the Winograd kernel loads its halo through a buffer descriptor and cannot
+    address it, so the planner gives the layer the halo layout AND the halo kernel (tests/test_conv_route_cpu.py states the
+    route).  Before the planner the weight-plane producer chose the Winograd layout, the Winograd launcher declined, and the
+    halo kernel read 12 transformed taps as 9 direct ones: forward and data gradient silently wrong — error 0.98 (y) / 1.25 (dx) of the
+    reference's largest magnitude on these patches, measured on the commit before the planner.  Compared on patches (the four
+    corners, an interior patch, the last rows: the highest addresses) with an fp64 convolution of the matching crop, at the
+    bound this file holds every f16x2 convolution to."""
+    from ever_amd.hip import functional as F
+    n, c, h, w = 1, 256, 1450, 1450
+    g = torch.Generator(device=cuda).manual_seed(5)
+    x = (torch.randn(n, h, w, c, generator=g, device=cuda) + 0.5).permute(0, 3, 1, 2).requires_grad_()     # channels_last
+    gy = (torch.randn(n, h, w, c, generator=g, device=cuda) + 0.25).permute(0, 3, 1, 2)
+    wt = ((torch.randn(c, c, 3, 3, generator=torch.Generator().manual_seed(6)) + 0.1) / (c * 9) ** 0.5)
+    prev = F.set_conv_math('f16x2')
+    try:
+        y = F.conv2d(x, wt.to(cuda).contiguous(memory_format=torch.channels_last), None, padding=1)
+        y.backward(gy)
+        torch.cuda.synchronize()
+    finally:
+        F.set_conv_math(prev)
+    w64 = wt.double()
+    patches = [(0, 32, 0, 32), (0, 32, w - 32, w), (h - 32, h, 0, 32), (h - 32, h, w - 32, w), (700, 732, 700, 732), (h - 4, h, 0, w)]
+    err = {'y': 0.0, 'dx': 0.0}
+    top = {'y': 0.0, 'dx': 0.0}
+    for y0, y1, x0, x1 in patches:
+        iy0, iy1, ix0, ix1 = max(y0 - 1, 0), min(y1 + 1, h), max(x0 - 1, 0), min(x1 + 1, w)
+        crop = lambda t: t.detach()[:, :, iy0:iy1, ix0:ix1].cpu().double()
+        inner = lambda t: t[:, :, y0 - iy0:y1 - iy0, x0 - ix0:x1 - ix0]   # (rows next to a cut edge of the crop miss a neighbour)
+        for name, got, ref in (('y', y, TF.conv2d(crop(x), w64, None, padding=1)),
+                               ('dx', x.grad, TF.conv_transpose2d(crop(gy), w64, None, padding=1))):
+            err[name] = max(err[name], (inner(crop(got)) - inner(ref)).abs().max().item())
+            top[name] = max(top[name], inner(ref).abs().max().item())
+    rel = {k: err[k] / top[k] for k in err}
+    print('largest error on the patches, relative to the reference\'s largest magnitude there:', rel)
+    assert rel['y'] < 5e-6 and rel['dx'] < 5e-6, rel

@@ -112,7 +112,13 @@ def main():
         base = timeit(fn, iters)
         ref = out.clone()
         res = {}
-        halo_layer = kh == 3 and os.environ.get('EVK_X3_HALO', '1') != '0' and key[9] == 1 and key[13] == 1
+        # which force string applies is the planner's call (the plane layout of the launch), not re-derived here
+        layout = ctypes.c_int32(0)
+        name = ctypes.create_string_buffer(128)
+        _C.call('evk_conv2d_route', ctypes.byref(d), 0 if for_dgrad else -1, 2, 0, 1 if kind == 'dgrad_accum' else 0,
+                1 if kind == 'fwd_stats' else 0, torch.cuda.get_device_properties(0).multi_processor_count // 8, name, len(name),
+                ctypes.byref(layout))
+        halo_layer = layout.value != 0
         for cfg in (HALO if halo_layer else GENERIC):
             os.environ['EVK_X3_HALO_FORCE' if halo_layer else 'EVK_X3_FORCE'] = cfg
             try:
