@@ -47,6 +47,7 @@ SIGNATURES = {
     'evk_conv2d_split_jobs': (c_int, [_DP, P, c_i32, P, _JP, c_i32]),
     'evk_split_job_pairs': (c_i64, [_JP]),
     'evk_conv2d_route': (c_int, [_DP, c_i32, c_i32, c_u32, c_i32, c_i32, c_i32, C.c_char_p, c_size_t, C.POINTER(c_i32)]),
+    'evk_conv2d_wgrad_route': (c_int, [_DP, c_i32, c_u32, C.c_char_p, c_size_t, C.POINTER(c_i32)]),
     'evk_conv2d_split_multi': (c_int, [P, P, c_i32, P]),
     'evk_conv2d_fwd_x3': (c_int, [_DP, P, P, P, P, c_u32, P]),
     'evk_conv2d_stats_max_parts': (c_i32, [_DP]),

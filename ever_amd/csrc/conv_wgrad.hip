@@ -296,6 +296,7 @@ WGradPlan plan_wgrad(const evk_conv_desc* d, int x3, int planes, int tr, int sha
   pl.ws = (x3 && ws_mode && d->Cout >= ws_min && Ktot >= 256 && fits32) ? 1 : 0;
   if (tr) { pl.ws = 1; pl.bm = 128; }
   if (pl.ws) pl.bn = 256;
+  if (tr == 2) pl.bn = 9 * 64;   // nine taps x 64 input channels per tile (tiles_k = Cin / 64 below)
   pl.tiles_co = ceil_div(d->Cout, pl.bm);
   pl.tiles_k = tr == 2 ? d->Cin / 64 : ceil_div(Ktot, pl.bn);
   const int tiles = pl.tiles_co * pl.tiles_k;
@@ -370,29 +371,73 @@ static size_t wgrad_ws_bytes(const evk_conv_desc* d, int x3) {
 extern "C" size_t evk_conv2d_wgrad_workspace_bytes(const evk_conv_desc* d) { return wgrad_ws_bytes(d, 0); }
 extern "C" size_t evk_conv2d_wgrad_x3_workspace_bytes(const evk_conv_desc* d) { return wgrad_ws_bytes(d, 1); }
 
+namespace evk {
+
+// The one decision of the weight-gradient family: arithmetic + operand flags + descriptor -> kernel, tile, operand form, split.
+int route_wgrad(const evk_conv_desc* d, int planes, uint32_t flags, WGradRoute* r) {
+  EVK_REQUIRE(d && r, EVK_E_INVALID, "conv2d_wgrad: null pointer");
+  EVK_REQUIRE(planes >= 0 && planes <= 3, EVK_E_INVALID, "conv2d_wgrad: arithmetic %d (0 fp32, 1 bf16, 2 f16x2, 3 bf16x3)", planes);
+  EVK_REQUIRE(d->Cin % 4 == 0 && d->Cout % 4 == 0, EVK_E_UNSUPPORTED,
+              "conv2d_wgrad: Cin=%d and Cout=%d must be multiples of 4", d->Cin, d->Cout);
+  EVK_REQUIRE((long long)d->N * d->H * d->W * d->Cin < 0x7fffffffLL &&
+                  (long long)d->N * d->Ho * d->Wo * d->Cout < 0x7fffffffLL,
+              EVK_E_UNSUPPORTED, "conv2d_wgrad: tensors of 2^31 or more elements are not supported");
+  EVK_REQUIRE(planes == 2 || flags == 0, EVK_E_INVALID, "conv2d_wgrad: flags 0x%x belong to the f16x2 arithmetic", flags);
+  const int planar = (flags & (EVK_CONV_X_PLANAR | EVK_CONV_DY_PLANAR)) ? 1 : 0;
+  EVK_REQUIRE(!planar || ((flags & EVK_CONV_X_PLANAR) && (flags & EVK_CONV_DY_PLANAR) && planes == 2),
+              EVK_E_UNSUPPORTED, "conv2d_wgrad: planar operands come in pairs (x and dy), f16x2 only, no bias gradient");
+  EVK_REQUIRE(!planar || wgrad_tr_applicable(d, planes), EVK_E_UNSUPPORTED,
+              "conv2d_wgrad: planar operands need Cin %% 64 == 0, Cout %% 64 == 0 and Wo %% 8 == 0 "
+              "(Cin=%d Cout=%d Wo=%d) and tensors below 2 GiB", d->Cin, d->Cout, d->Wo);
+  const int x3 = planes != 0;
+  const int nine = planar && wgrad_tr_nine_tap(d) ? 1 : 0;
+  WGradRoute o{};
+  o.plan = plan_wgrad(d, x3, x3 ? planes : 3, planar ? 1 + nine : 0, (flags & EVK_CONV_WGRAD_SHARED) ? 1 : 0);
+  o.kernel = planar ? WGradKernel::Tr : !x3 ? WGradKernel::Fp32 : o.plan.ws ? WGradKernel::X3Ws : WGradKernel::X3;
+  o.pkx = (flags & EVK_CONV_X_PACKED) ? 1 : 0;
+  o.pkd = (flags & EVK_CONV_DY_PACKED) ? 1 : 0;
+  o.w8 = d->Wo % 8 == 0;
+  o.nt = nine ? 9 : 1;
+  // (the wave-specialised kernel takes the packed operands as two booleans, the single-role tiles as a fourth operand form)
+  o.npx = planes == 2 && (o.pkx || o.pkd) && o.kernel == WGradKernel::X3 ? 4 : planes;
+  *r = o;
+  return EVK_OK;
+}
+
+// ---- the route as a kernel trace spells it
+void wgrad_kernel_name(const WGradRoute& r, char* buf, size_t n) {
+  auto tf = [](int v) { return v ? "true" : "false"; };
+  switch (r.kernel) {
+    case WGradKernel::Fp32: snprintf(buf, n, "conv_wgrad_kernel<%d, %d, 2, 2>", r.plan.bm, r.plan.bn); break;
+    case WGradKernel::X3: snprintf(buf, n, "conv_wgrad_x3_kernel<%d, %d, 2, 2, %d>", r.plan.bm, r.plan.bn, r.npx); break;
+    case WGradKernel::X3Ws:
+      snprintf(buf, n, "conv_wgrad_x3ws_kernel<%d, %d, %d, %s, %s, %s>", r.plan.bm, r.plan.bn, r.npx, tf(r.w8), tf(r.pkx), tf(r.pkd));
+      break;
+    case WGradKernel::Tr: snprintf(buf, n, "conv_wgrad_tr_kernel<%d>", r.nt); break;
+  }
+}
+
+}  // namespace evk
+
 static int conv_wgrad_any(const evk_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias,
                           void* workspace, size_t workspace_bytes, void* stream, int x3, int planes = 3,
                           const uint32_t* x_scale = nullptr, const uint32_t* dy_scale = nullptr, uint32_t pk_flags = 0) {
   EVK_REQUIRE(d && x && dy && dw, EVK_E_INVALID, "conv2d_wgrad: null pointer");
-  EVK_REQUIRE(d->Cin % 4 == 0 && d->Cout % 4 == 0, EVK_E_UNSUPPORTED,
-              "conv2d_wgrad: Cin=%d and Cout=%d must be multiples of 4", d->Cin, d->Cout);
+  WGradRoute route;
+  int rc = route_wgrad(d, x3 ? planes : 0, pk_flags, &route);
+  if (rc) return rc;
+  const WGradPlan& pl = route.plan;
   EVK_REQUIRE(workspace_bytes >= wgrad_ws_bytes(d, x3) && (workspace || workspace_bytes == 0), EVK_E_WORKSPACE,
-              "conv2d_wgrad: workspace %zu < %zu", workspace_bytes, wgrad_ws_bytes(d, x3));
-  EVK_REQUIRE((long long)d->N * d->H * d->W * d->Cin < 0x7fffffffLL &&
-                  (long long)d->N * d->Ho * d->Wo * d->Cout < 0x7fffffffLL,
-              EVK_E_UNSUPPORTED, "conv2d_wgrad: tensors of 2^31 or more elements are not supported");
+              "conv2d_wgrad: workspace %zu < %zu", workspace_bytes, wgrad_ws_bytes(d, x3));   // (sized over every plan of the arithmetic)
   hipStream_t st = (hipStream_t)stream;
-  const int planar = (pk_flags & (EVK_CONV_X_PLANAR | EVK_CONV_DY_PLANAR)) ? 1 : 0;   // (workspace: sized for the unshared plan, which splits more)
-  EVK_REQUIRE(!planar || ((pk_flags & EVK_CONV_X_PLANAR) && (pk_flags & EVK_CONV_DY_PLANAR) && planes == 2 && !dbias),
-              EVK_E_UNSUPPORTED, "conv2d_wgrad: planar operands come in pairs (x and dy), f16x2 only, no bias gradient");
-  const int nine = planar && wgrad_tr_nine_tap(d) ? 1 : 0;
-  const WGradPlan pl = plan_wgrad(d, x3, planes, planar ? 1 + nine : 0, (pk_flags & EVK_CONV_WGRAD_SHARED) ? 1 : 0);
+  const int planar = route.kernel == WGradKernel::Tr ? 1 : 0;
+  EVK_REQUIRE(!(planar && dbias), EVK_E_UNSUPPORTED, "conv2d_wgrad: planar operands come in pairs (x and dy), f16x2 only, no bias gradient");
   WGradArgs a{};
   a.planes = planes;
   a.planar = planar;
   a.x_scale = x_scale; a.dy_scale = dy_scale;
-  a.x_packed = (pk_flags & EVK_CONV_X_PACKED) ? 1 : 0;
-  a.dy_packed = (pk_flags & EVK_CONV_DY_PACKED) ? 1 : 0;
+  a.x_packed = route.pkx;
+  a.dy_packed = route.pkd;
   EVK_REQUIRE(!(a.dy_packed && dbias), EVK_E_UNSUPPORTED, "conv2d_wgrad: the bias gradient needs dy as fp32");
   a.x = x; a.dy = dy;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
@@ -404,16 +449,16 @@ static int conv_wgrad_any(const evk_conv_desc* d, const float* x, const float* d
   a.fd_hw = make_fastdiv((uint32_t)(d->Ho * d->Wo));
   a.fd_w = make_fastdiv((uint32_t)d->Wo);
   a.out = pl.splitk > 1 ? (float*)workspace : dw;
-  int rc;
-  if (planar) {
-    EVK_REQUIRE(wgrad_tr_applicable(a), EVK_E_UNSUPPORTED, "conv2d_wgrad: planar operands need Cin %% 64 == 0 and Cout %% 64 == 0 "
-                "(Cin=%d Cout=%d) and tensors below 2 GiB", d->Cin, d->Cout);
-    rc = launch_wgrad_tr(a, nine, st);
-  } else if (x3) rc = launch_wgrad_x3(a, pl, st);
-  else if (pl.bm == 128 && pl.bn == 128) rc = launch_wgrad<128, 128, 2, 2>(a, st);
-  else if (pl.bm == 64 && pl.bn == 128) rc = launch_wgrad<64, 128, 2, 2>(a, st);
-  else if (pl.bm == 128 && pl.bn == 64) rc = launch_wgrad<128, 64, 2, 2>(a, st);
-  else rc = launch_wgrad<64, 64, 2, 2>(a, st);
+  switch (route.kernel) {
+    case WGradKernel::Tr: rc = launch_wgrad_tr(a, route, st); break;
+    case WGradKernel::X3:
+    case WGradKernel::X3Ws: rc = launch_wgrad_x3(a, route, st); break;
+    default:
+      if (pl.bm == 128 && pl.bn == 128) rc = launch_wgrad<128, 128, 2, 2>(a, st);
+      else if (pl.bm == 64 && pl.bn == 128) rc = launch_wgrad<64, 128, 2, 2>(a, st);
+      else if (pl.bm == 128 && pl.bn == 64) rc = launch_wgrad<128, 64, 2, 2>(a, st);
+      else rc = launch_wgrad<64, 64, 2, 2>(a, st);
+  }
   if (rc) return rc;
   if (pl.splitk > 1) {
     const size_t n = (size_t)d->Cout * a.Ktot;  // multiple of 4 since Cin % 4 == 0
@@ -478,4 +523,25 @@ extern "C" int evk_conv2d_wgrad_x3(const evk_conv_desc* d, const float* x, const
                                    void* workspace, size_t workspace_bytes, void* stream) {
   EVK_REQUIRE(d && d->Cin % 4 == 0 && d->Cout % 4 == 0, EVK_E_UNSUPPORTED, "conv2d_wgrad_x3: channels must be multiples of 4");
   return conv_wgrad_any(d, x, dy, dw, dbias, workspace, workspace_bytes, stream, 1);
+}
+
+// Host only: the instantiation and split plan a weight-gradient launch of this descriptor takes (include/ever_hip.h)
+extern "C" int evk_conv2d_wgrad_route(const evk_conv_desc* d, int32_t planes, uint32_t flags, char* buf, size_t buf_bytes,
+                                      int32_t* plan) {
+  EVK_REQUIRE(d && buf && buf_bytes > 0, EVK_E_INVALID, "conv2d_wgrad_route: null pointer");
+  EVK_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->kh > 0 && d->kw > 0 && d->stride_h > 0 &&
+                  d->stride_w > 0 && d->dil_h > 0 && d->dil_w > 0 && d->Cin > 0 && d->Cout > 0,
+              EVK_E_INVALID, "conv2d_wgrad_route: bad descriptor");
+  EVK_REQUIRE((flags & ~(EVK_CONV_X_PACKED | EVK_CONV_DY_PACKED | EVK_CONV_X_PLANAR | EVK_CONV_DY_PLANAR | EVK_CONV_WGRAD_SHARED)) == 0,
+              EVK_E_INVALID, "conv2d_wgrad_route: unknown flag 0x%x", flags);
+  buf[0] = 0;
+  WGradRoute r;
+  const int rc = route_wgrad(d, planes, flags, &r);
+  if (rc) return rc;
+  wgrad_kernel_name(r, buf, buf_bytes);
+  if (plan) {
+    plan[0] = r.plan.bm; plan[1] = r.plan.bn; plan[2] = r.plan.tiles_co;
+    plan[3] = r.plan.tiles_k; plan[4] = r.plan.splitk; plan[5] = r.plan.chunk;
+  }
+  return EVK_OK;
 }

@@ -292,9 +292,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_tr_kernel(const WGradArgs p) {
   }
 }
 
-bool wgrad_tr_applicable(const WGradArgs& a) {
-  return a.planes == 2 && a.Cin % 64 == 0 && a.Cout % 64 == 0 && a.Wo % 8 == 0 &&
-         (long long)a.N * a.H * a.W * a.Cin * 4 < 0x7fffffffLL && (long long)a.M * a.Cout * 4 < 0x7fffffffLL;
+bool wgrad_tr_applicable(const evk_conv_desc* d, int planes) {
+  return planes == 2 && d->Cin % 64 == 0 && d->Cout % 64 == 0 && d->Wo % 8 == 0 &&
+         (long long)d->N * d->H * d->W * d->Cin * 4 < 0x7fffffffLL && (long long)d->N * d->Ho * d->Wo * d->Cout * 4 < 0x7fffffffLL;
 }
 // the nine-tap form: 3x3, stride 1, padding 1, no dilation, image rows that are whole steps
 bool wgrad_tr_nine_tap(const evk_conv_desc* d) {
@@ -315,9 +315,9 @@ static int launch_tr(const WGradArgs& b, hipStream_t stream) {
   return check_launch("conv_wgrad_tr");
 }
 
-int launch_wgrad_tr(const WGradArgs& a, int nine_tap, hipStream_t stream) {
+int launch_wgrad_tr(const WGradArgs& a, const WGradRoute& r, hipStream_t stream) {
   WGradArgs b = a;
-  return nine_tap ? launch_tr<9>(b, stream) : launch_tr<1>(b, stream);
+  return r.nt == 9 ? launch_tr<9>(b, stream) : launch_tr<1>(b, stream);
 }
 
 // ---- stand-alone producers of the planar form (the fused ones are the BatchNorm passes' planar modes)

@@ -234,15 +234,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WGradArgs p) {
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
-static int launch_one(const WGradArgs& a, hipStream_t stream) {
+static int launch_one(const WGradArgs& a, int npx, hipStream_t stream) {
   const size_t lds = (size_t)3 * (BM + BN) * kRowBytes;
-  if (a.planes == 1) {
+  if (npx == 1) {
     hipLaunchKernelGGL((conv_wgrad_x3_kernel<BM, BN, WAVES_M, WAVES_N, 1>), dim3(a.tiles_co * a.tiles_k * a.splitk),
                        dim3(256), lds, stream, a);
-  } else if (a.planes == 2 && (a.x_packed || a.dy_packed)) {
+  } else if (npx == 4) {
     hipLaunchKernelGGL((conv_wgrad_x3_kernel<BM, BN, WAVES_M, WAVES_N, 4>), dim3(a.tiles_co * a.tiles_k * a.splitk),
                        dim3(256), lds, stream, a);
-  } else if (a.planes == 2) {
+  } else if (npx == 2) {
     hipLaunchKernelGGL((conv_wgrad_x3_kernel<BM, BN, WAVES_M, WAVES_N, 2>), dim3(a.tiles_co * a.tiles_k * a.splitk),
                        dim3(256), lds, stream, a);
   } else {
@@ -252,12 +252,12 @@ static int launch_one(const WGradArgs& a, hipStream_t stream) {
   return check_launch("conv_wgrad_x3");
 }
 
-int launch_wgrad_x3(const WGradArgs& a, const WGradPlan& pl, hipStream_t stream) {
-  if (pl.ws) return launch_wgrad_x3ws(a, stream);
-  if (pl.bm == 128 && pl.bn == 128) return launch_one<128, 128, 2, 2>(a, stream);
-  if (pl.bm == 64 && pl.bn == 128) return launch_one<64, 128, 2, 2>(a, stream);
-  if (pl.bm == 128 && pl.bn == 64) return launch_one<128, 64, 2, 2>(a, stream);
-  return launch_one<64, 64, 2, 2>(a, stream);
+int launch_wgrad_x3(const WGradArgs& a, const WGradRoute& r, hipStream_t stream) {
+  if (r.kernel == WGradKernel::X3Ws) return launch_wgrad_x3ws(a, r, stream);
+  if (r.plan.bm == 128 && r.plan.bn == 128) return launch_one<128, 128, 2, 2>(a, r.npx, stream);
+  if (r.plan.bm == 64 && r.plan.bn == 128) return launch_one<64, 128, 2, 2>(a, r.npx, stream);
+  if (r.plan.bm == 128 && r.plan.bn == 64) return launch_one<128, 64, 2, 2>(a, r.npx, stream);
+  return launch_one<64, 64, 2, 2>(a, r.npx, stream);
 }
 
 }  // namespace evk

@@ -430,12 +430,12 @@ static int launch_wgrad_x3ws_t(const WGradArgs& b, hipStream_t stream) {
   return check_launch("conv_wgrad_x3ws");
 }
 
-int launch_wgrad_x3ws(const WGradArgs& a, hipStream_t stream) {
+int launch_wgrad_x3ws(const WGradArgs& a, const WGradRoute& r, hipStream_t stream) {
   WGradArgs b = a;
-  const bool w8 = (a.Wo & 7) == 0;
-  if (a.planes == 1) return w8 ? launch_wgrad_x3ws_t<1, true>(b, stream) : launch_wgrad_x3ws_t<1, false>(b, stream);
-  if (a.planes == 2) {
-    const int pk = (a.x_packed ? 1 : 0) | (a.dy_packed ? 2 : 0);
+  const bool w8 = r.w8 != 0;
+  if (r.npx == 1) return w8 ? launch_wgrad_x3ws_t<1, true>(b, stream) : launch_wgrad_x3ws_t<1, false>(b, stream);
+  if (r.npx == 2) {
+    const int pk = (r.pkx ? 1 : 0) | (r.pkd ? 2 : 0);
     if (pk == 3) return w8 ? launch_wgrad_x3ws_t<2, true, true, true>(b, stream) : launch_wgrad_x3ws_t<2, false, true, true>(b, stream);
     if (pk == 2) return w8 ? launch_wgrad_x3ws_t<2, true, false, true>(b, stream) : launch_wgrad_x3ws_t<2, false, false, true>(b, stream);
     if (pk == 1) return w8 ? launch_wgrad_x3ws_t<2, true, true, false>(b, stream) : launch_wgrad_x3ws_t<2, false, true, false>(b, stream);

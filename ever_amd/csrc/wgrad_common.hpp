@@ -34,10 +34,25 @@ struct WGradPlan {
 // tr = 1 / 2: the planar-operand kernel (conv_wgrad_tr.hip), one workgroup per CU: 128 x 256 tile / nine-tap form
 // (128 output channels x 9 taps x 64 input channels per tile)
 WGradPlan plan_wgrad(const evk_conv_desc* d, int x3, int planes = 3, int tr = 0, int shared = 0);
-int launch_wgrad_x3(const WGradArgs& a, const WGradPlan& pl, hipStream_t stream);
-int launch_wgrad_x3ws(const WGradArgs& a, hipStream_t stream);
-bool wgrad_tr_applicable(const WGradArgs& a);
+
+// Which instantiation a weight-gradient launch takes, decided ONCE (route_wgrad, conv_wgrad.hip): the launchers below switch
+// on this value and evk_conv2d_wgrad_route prints it — there is no second copy of the decision.
+enum class WGradKernel { Fp32, X3, X3Ws, Tr };
+struct WGradRoute {
+  WGradKernel kernel;
+  int npx;            // operand form of the split kernels (NP / NPX): 1 bf16, 2 f16x2, 3 bf16x3, 4 f16x2 with a packed operand
+  int w8, pkx, pkd;   // X3Ws: Wo % 8 == 0; x / dy arrive packed
+  int nt;             // Tr: 1 (segments) or 9 (nine-tap halo form)
+  WGradPlan plan;     // tile (bm x bn) and split
+};
+// planes: 0 the fp32 kernel, 1 bf16, 2 f16x2, 3 bf16x3; flags: EVK_CONV_{X,DY}_{PACKED,PLANAR}, EVK_CONV_WGRAD_SHARED.
+// EVK_OK, or the error (with evk_last_error set) the launch entry points report for the same descriptor and flags.
+int route_wgrad(const evk_conv_desc* d, int planes, uint32_t flags, WGradRoute* r);
+void wgrad_kernel_name(const WGradRoute& r, char* buf, size_t n);
+int launch_wgrad_x3(const WGradArgs& a, const WGradRoute& r, hipStream_t stream);
+int launch_wgrad_x3ws(const WGradArgs& a, const WGradRoute& r, hipStream_t stream);
+bool wgrad_tr_applicable(const evk_conv_desc* d, int planes);
 bool wgrad_tr_nine_tap(const evk_conv_desc* d);
-int launch_wgrad_tr(const WGradArgs& a, int nine_tap, hipStream_t stream);
+int launch_wgrad_tr(const WGradArgs& a, const WGradRoute& r, hipStream_t stream);
 
 }  // namespace evk

@@ -62,7 +62,7 @@ typedef struct evk_conv_desc {
 /* PLANAR operands of the f16x2 arithmetic (round 3): the same (h, l) pair of value / s, stored as two fp16 planes —
  * H[M][C] followed by L[M][C] in one allocation of the fp32 tensor's size (evk_pack_planar_f16x2).  The weight gradient
  * then stages nothing: both operands go global -> LDS by DMA and the fragments come from transposing LDS reads
- * (csrc/conv_wgrad_tr.hip).  Needs both flags, Cin % 64 == 0, Cout % 64 == 0, dbias == NULL. */
+ * (csrc/conv_wgrad_tr.hip).  Needs both flags, Cin % 64 == 0, Cout % 64 == 0, Wo % 8 == 0, dbias == NULL. */
 #define EVK_CONV_X_PLANAR 8u
 #define EVK_CONV_DY_PLANAR 16u
 /* evk_conv2d_wgrad_f16x2_ex only (round 5): the launch runs BESIDE other work on another stream (the weight-gradient side stream
@@ -124,6 +124,17 @@ int64_t evk_split_job_pairs(const evk_split_job* job /* host */);
  * F(2,3) — which is the layout evk_conv2d_split_weight* / evk_conv2d_split_jobs produce for the same descriptor. */
 int evk_conv2d_route(const evk_conv_desc* d, int32_t cls, int32_t planes, uint32_t flags, int32_t with_accum,
                      int32_t with_stats, int32_t cus_per_xcd, char* buf, size_t buf_bytes, int32_t* layout);
+/* Host only, the same for the third launch of a convolution, the weight gradient: which instantiation and which split-K plan
+ * evk_conv2d_wgrad (planes 0), _bf16 (1), _f16x2 / _f16x2_ex (2) or _x3 (3) take for this descriptor.  flags: those of
+ * evk_conv2d_wgrad_f16x2_ex (EVK_CONV_X/DY_PACKED, EVK_CONV_X/DY_PLANAR, EVK_CONV_WGRAD_SHARED; planes 2 only).  Writes the
+ * kernel as a trace spells it ("conv_wgrad_x3ws_kernel<128, 256, 2, true, false, true>", "conv_wgrad_tr_kernel<9>") and, if
+ * plan is not NULL, plan[6] = tile rows (output channels), tile columns (k = taps x Cin; nine-tap planar form: 9 taps x 64
+ * channels), row tiles, column tiles, splits of the pixel reduction, pixels per split.  The grid is row tiles x column
+ * tiles x splits; with more than one split the partial tiles go to the workspace ([splits][Cout][kh kw Cin] floats) and are
+ * summed in a fixed order.  Returns the error the launch would for the same descriptor and flags (planar operands without
+ * their pair, Cin % 64, Wo % 8, ...): the launch entry points take kernel, tile and operand form from the value this prints. */
+int evk_conv2d_wgrad_route(const evk_conv_desc* d, int32_t planes, uint32_t flags, char* buf, size_t buf_bytes,
+                           int32_t* plan /* NULL or int32[6] */);
 int evk_conv2d_split_multi(const evk_split_job* jobs_dev, const int32_t* block_map_dev, int32_t nblocks,
                            void* stream);
 int evk_conv2d_fwd_x3(const evk_conv_desc* d, const float* x, const void* wsplit, const float* bias,

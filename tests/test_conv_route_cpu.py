@@ -5,6 +5,7 @@ tests/golden/conv_routes.json is a kernel trace of the commit BEFORE the planner
 that differ under each other switch setting.  The planner must name the same instantiation for every one of them."""
 import ctypes
 import json
+import math
 import os
 import subprocess
 import sys
@@ -127,3 +128,33 @@ def test_route_entry_point_checks_its_arguments():
     # 1x1 stride 2: only residue class (0, 0) has a tap
     d = _C.ConvDesc(16, 128, 128, 256, 64, 64, 512, 1, 1, 2, 2, 0, 0, 1, 1)
     assert [route(lib, d, c, 2)[0] != '' for c in range(4)] == [True, False, False, False]
+
+
+def test_empty_residue_classes_are_exactly_those_no_tap_reaches():
+    """Data gradient of a strided (and dilated) convolution: input position i = c + j * stride receives output o through tap k
+    iff i + pad == o * stride + k * dil.  evk_conv2d_route answers "no launch" for the residue class (cy, cx) exactly when brute
+    force over the map finds no such (i, k, o) on one of the two axes — strides 1..4, dilations 1..6, kernels 1..7, paddings
+    0..2 dil, a different combination on each axis (the gcd(dil, stride) > 1 branch of plan_axis included)."""
+    lib = _C.load()
+    size = 64
+    axes = [(s, dil, k, pad) for s in range(1, 5) for dil in range(1, 7) for k in range(1, 8) for pad in range(0, 2 * dil + 1)]
+
+    def reached(c, s, dil, k, pad):
+        out = (size + 2 * pad - dil * (k - 1) - 1) // s + 1
+        return any((i + pad - t * dil) % s == 0 and 0 <= (i + pad - t * dil) // s < out for i in range(c, size, s) for t in range(k))
+
+    n_empty = n_gcd = n = 0
+    for j, (sh, dh, kh, ph) in enumerate(axes):
+        sw, dw, kw, pw = axes[(j * 577 + 131) % len(axes)]     # (577 is coprime to the list's length: every combination on both axes)
+        ho, wo = (size + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (size + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+        d = _C.ConvDesc(1, size, size, 64, ho, wo, 64, kh, kw, sh, sw, ph, pw, dh, dw)
+        for cy in range(sh):
+            for cx in range(sw):
+                want = reached(cy, sh, dh, kh, ph) and reached(cx, sw, dw, kw, pw)
+                got = route(lib, d, cy * sw + cx, 3)[0] != ''
+                assert got == want, ((sh, dh, kh, ph), (sw, dw, kw, pw), (cy, cx), got, want)
+                n += 1
+                n_empty += not want
+                n_gcd += (not want) and ((cy + ph) % math.gcd(dh, sh) != 0 or (cx + pw) % math.gcd(dw, sw) != 0)
+    assert len({a for a in axes}) == len(axes) and math.gcd(577, len(axes)) == 1
+    assert n > 8000 and n_empty > 1000 and n_gcd > 1000, (n, n_empty, n_gcd)

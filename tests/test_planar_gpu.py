@@ -48,7 +48,18 @@ CASES = [
     (3, 256, 16, 24, 128, 1, 1, 0),     # 1x1
     (2, 128, 32, 32, 256, 1, 2, 0),     # strided 1x1 shortcut
     (1, 64, 8, 40, 64, 3, 1, 1),        # rows that wrap inside a step, pixel count not a multiple of the chunk
+    (1, 256, 48, 48, 256, 3, 1, 1),     # 18 tiles x 2304 pixels: 9 chunks of 256, but 7 of 352 when the launch shares the chip
 ]
+# the shapes above on which EVK_CONV_WGRAD_SHARED changes the split (evk_conv2d_wgrad_route says so, asserted below): on all
+# the others ceil(M / 256) caps the split count far below the slot count and the flag changes nothing
+SHARED_SPLITS_DIFFERENTLY = {(1, 256, 48, 48, 256, 3, 1, 1)}
+
+
+def _plan(lib, d, flags):
+    buf = ctypes.create_string_buffer(128)
+    plan = (ctypes.c_int32 * 6)()
+    assert lib.evk_conv2d_wgrad_route(ctypes.byref(d), 2, flags, buf, len(buf), plan) == 0, lib.evk_last_error()
+    return buf.value.decode(), tuple(plan)
 
 
 @pytest.mark.parametrize('case', CASES, ids=lambda c: 'x'.join(map(str, c)))
@@ -91,6 +102,8 @@ def test_planar_weight_gradient(cuda, case):
     # EVK_CONV_WGRAD_SHARED (32): the launch shares the chip with another stream — the wide-tile kernels split for half of the
     # CUs.  Same workspace, same result to the accumulation order, both operand forms
     for flags, src in ((8 | 16, (xq, dq)), (2 | 4, (xp, dp))):
+        (name, plan), (name_sh, plan_sh) = _plan(lib, d, flags), _plan(lib, d, flags | 32)
+        assert name_sh == name and (plan_sh[4:] != plan[4:]) == (case in SHARED_SPLITS_DIFFERENTLY), (flags, name, plan, plan_sh)
         dw_sh = torch.full_like(dw_planar, float('nan'))
         _C.call('evk_conv2d_wgrad_f16x2_ex', ctypes.byref(d), src[0].data_ptr(), bx.data_ptr(), src[1].data_ptr(), bd.data_ptr(),
                 dw_sh.data_ptr(), None, ws.data_ptr(), wsb, flags | 32, st)
