@@ -93,6 +93,7 @@ SIGNATURES = {
     'evk_nchw_to_nhwc': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_nhwc_to_nchw': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_bn_workspace_bytes': (c_size_t, [c_i64, c_i32]),
+    'evk_bn_plan': (c_int, [c_i64, c_i32, c_i32, C.POINTER(c_i32)]),
     'evk_bn_fwd_train': (c_int, [P, P, P, P, P, P, c_f32, c_f32, P, P, P, c_i64, c_i32, c_u32, P, c_size_t, P, P]),
     'evk_bn_fwd_train_parts': (c_int, [P, P, P, P, P, P, c_f32, c_f32, P, P, P, c_i64, c_i32, c_u32, P, c_i32, P, c_size_t, P, P]),
     'evk_bn_fwd_train_parts_bits': (c_int, [P, P, P, P, P, P, c_f32, c_f32, P, P, P, c_i64, c_i32, c_u32, P, c_i32, P, c_size_t, P, P, P]),

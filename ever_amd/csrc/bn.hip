@@ -956,15 +956,19 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const float* __r
 
 static unsigned oneshot_grid(size_t n4) { return (unsigned)((n4 + 255) / 256); }
 
+// record lanes per channel of the merge: bn_parts_final_kernel<256 / lanes, lanes>
+static int parts_final_lanes(int nparts) { return nparts >= 1024 ? 256 : (nparts >= 512 ? 128 : 32); }
+
 static void launch_parts_final(hipStream_t st, const float* parts, int nparts, int C, double rows, const float* gamma,
                                const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                                float* save_mean, float* save_invstd, float* scale_shift, uint32_t* amax, int pack) {
   // one channel per workgroup above 1024 records — eight records per lane, all in flight at once (level with the two-channel
   // form on the step, ahead in the family: 407 vs 460 us per step)
-  if (nparts >= 1024)
+  const int fl = parts_final_lanes(nparts);
+  if (fl == 256)
     hipLaunchKernelGGL((bn_parts_final_kernel<1, 256>), dim3(C), dim3(256), 0, st, parts, nparts, C, rows, gamma, beta,
                        running_mean, running_var, momentum, eps, save_mean, save_invstd, scale_shift, amax, pack);
-  else if (nparts >= 512)
+  else if (fl == 128)
     hipLaunchKernelGGL((bn_parts_final_kernel<2, 128>), dim3((C + 1) / 2), dim3(256), 0, st, parts, nparts, C, rows, gamma, beta,
                        running_mean, running_var, momentum, eps, save_mean, save_invstd, scale_shift, amax, pack);
   else
@@ -980,6 +984,46 @@ extern "C" size_t evk_bn_workspace_bytes(int64_t rows, int32_t C) {
   if (rows <= 0 || C <= 0) return 0;
   // partial sums [blocks][2][C], 8 C of coefficients, per-block maxima [blocks][2][C] (packed outputs)
   return ((size_t)kMaxStatBlocks * 4 * C + 8 * (size_t)C) * sizeof(float);
+}
+
+// the pool backward's split of an even map into quads: as many workgroups as its row plan
+static void bn_quad_split(int64_t rows, const BnPlan& pl, int& nblk, int& qpb) {
+  const int quads = (int)(rows / 4);
+  qpb = (quads + pl.nblk - 1) / pl.nblk;
+  qpb = ((qpb + pl.rl - 1) / pl.rl) * pl.rl;
+  nblk = (quads + qpb - 1) / qpb;
+}
+
+// Host only (no launch): the plan the reduce passes take for a [rows][C] map.  kind 0: evk_bn_fwd_train / evk_bn_bwd / the
+// staged entry points; kind 1: evk_bn_relu_pool_bwd.  out = {nblk, rows_per_blk, tpc, rl, quad nblk, quads per workgroup}
+// (the last two: the split of an even map into 2 x 2 quads, kind 1 with rows % 4 == 0, else 0).  kind 2: the merge of `rows`
+// statistics records (launch_parts_final): out = {workgroups, 0, channels per workgroup, record lanes per channel, 0, 0}.
+extern "C" int evk_bn_plan(int64_t rows, int32_t C, int32_t kind, int32_t* out) {
+  EVK_REQUIRE(out, EVK_E_INVALID, "bn_plan: null pointer");
+  EVK_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && C <= 2048 && kind >= 0 && kind <= 2 && (kind == 0 || rows < 0x7fffffffLL),
+              EVK_E_UNSUPPORTED, "bn_plan: rows=%lld C=%d kind=%d", (long long)rows, C, kind);
+  if (kind == 2) {
+    const int fl = parts_final_lanes((int)rows), fc = 256 / fl;
+    out[0] = (C + fc - 1) / fc;
+    out[2] = fc;
+    out[3] = fl;
+    out[1] = out[4] = out[5] = 0;
+    return EVK_OK;
+  }
+  const BnPlan pl = kind ? bn_plan(rows, C, 65536, kMaxStatBlocks) : bn_plan(rows, C);
+  EVK_REQUIRE(pl.rows_per_blk <= 0x7fffffffLL, EVK_E_UNSUPPORTED, "bn_plan: rows=%lld do not fit the answer", (long long)rows);
+  out[0] = pl.nblk;
+  out[1] = (int32_t)pl.rows_per_blk;
+  out[2] = pl.tpc;
+  out[3] = pl.rl;
+  out[4] = out[5] = 0;
+  if (kind == 1 && rows % 4 == 0) {
+    int nblk, qpb;
+    bn_quad_split(rows, pl, nblk, qpb);
+    out[4] = nblk;
+    out[5] = qpb;
+  }
+  return EVK_OK;
 }
 
 
@@ -1097,9 +1141,8 @@ extern "C" int evk_bn_relu_pool_bwd(const float* dp, const uint8_t* code, const 
   const bool quad = (H % 2 == 0) && (W % 2 == 0);
   // quads in place of rows, as many workgroups as the row plan (a quad is four rows' worth of elements)
   const int quads = (int)(rows / 4);
-  int qpb = (quads + pl.nblk - 1) / pl.nblk;
-  qpb = ((qpb + pl.rl - 1) / pl.rl) * pl.rl;
-  const int nblk = quad ? (quads + qpb - 1) / qpb : pl.nblk;
+  int nblk = pl.nblk, qpb = 0;
+  if (quad) bn_quad_split(rows, pl, nblk, qpb);
   if (quad)
     hipLaunchKernelGGL(bn_pool_bwd_partial_quad_kernel, dim3(nblk), dim3(256), 0, st, dp, code, x, save_mean, save_invstd,
                        gamma, beta, partial, quads, H, W, C, Ho, Wo, qpb, pl.tpc, pl.rl);

@@ -315,6 +315,15 @@ int evk_nhwc_to_nchw(const float* src, float* dst, int32_t N, int32_t C, int32_t
  * the bit is ignored.) */
 #define EVK_BN_NO_FUSE 8u
 size_t evk_bn_workspace_bytes(int64_t rows, int32_t C);
+/* Host only, no launch: how the reduce passes split a [rows][C] map (tests pick their shapes with it).  kind 0: the plan of
+ * evk_bn_fwd_train, evk_bn_bwd and the staged entry points; kind 1: the plan of evk_bn_relu_pool_bwd.
+ * out[6] = { workgroups, rows per workgroup, threads per row (each walks C / 4 / tpc 16-byte chunks), rows in flight per
+ * workgroup, and for kind 1 with rows % 4 == 0 the split an even map takes: workgroups, 2 x 2 quads per workgroup (else 0, 0) }.
+ * kind 2: the merge of `rows` statistics records (evk_bn_fwd_train_parts, evk_bn_finalize_parts, the fused stem pass):
+ * out = { workgroups, 0, channels per workgroup, record lanes per channel, 0, 0 }.
+ * A workgroup's partial record is [2][C] floats; the workspace holds records, 8 C coefficients and, for packed dx, as many
+ * records of maxima, in that order. */
+int evk_bn_plan(int64_t rows, int32_t C, int32_t kind, int32_t* out);
 int evk_bn_fwd_train(const float* x, const float* residual, const float* gamma, const float* beta,
                      float* running_mean, float* running_var, float momentum, float eps,
                      float* y, float* save_mean, float* save_invstd, int64_t rows, int32_t C,

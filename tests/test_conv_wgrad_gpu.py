@@ -16,12 +16,11 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+from tests.guard_common import guarded as _guarded, guards_intact as _guards_intact
 from tests.wgrad_plan_common import DY_PACKED, PLANAR, SHARED, X_PACKED, conv_desc, fields, planar_ok, wgrad_route
 
 pytestmark = pytest.mark.gpu
 
-PAD = 64            # floats of sentinel on either side of dw and of the workspace (keeps 256-byte alignment)
-SENTINEL = 12345.0
 BF16_GRADE = 2e-2   # tests/test_bf16_mode_gpu.py
 
 # form -> (arithmetic of evk_conv2d_wgrad_route, flags)
@@ -170,18 +169,6 @@ def _bits(lib, t, aws, st):
     b = torch.zeros(int(lib.evk_absmax_words()), dtype=torch.int32, device=t.device)
     _C.call('evk_absmax', t.data_ptr(), t.numel(), b.data_ptr(), aws.data_ptr(), st)
     return b
-
-
-def _guarded(n, device):
-    """a NaN-filled slice of n floats inside a sentinel-filled allocation"""
-    whole = torch.full((n + 2 * PAD,), SENTINEL, device=device)
-    inner = whole[PAD:PAD + n]
-    inner.fill_(float('nan'))
-    return whole, inner
-
-
-def _guards_intact(whole, n):
-    return bool((whole[:PAD] == SENTINEL).all() and (whole[PAD + n:] == SENTINEL).all())
 
 
 def _rel(a, ref):
