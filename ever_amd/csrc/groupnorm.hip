@@ -7,7 +7,7 @@
 // BatchNorm-style pivot shift, stage 2 folds the channels of a group in fp64.  Backward mirrors it:
 // per-(sample, chunk, channel) sums of dy and dy*xhat, folded per group (for dx) and per channel (dgamma,
 // dbeta) in fp64, then one apply pass.  HBM-bound: 3|x| forward, 5|x| backward, 16-byte accesses.
-#include "common.hpp"
+#include "bn_common.hpp"   // relu_mask
 
 namespace evk {
 
@@ -75,8 +75,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
           f32x4 g = *reinterpret_cast<const f32x4*>(dn + o);
           if (relu) {
             const f32x4 yy = *reinterpret_cast<const f32x4*>(yn + o);
-            g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
-            g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
+            g = relu_mask(g, yy);
           }
           s += g;
           q += g * ((xv - mu) * is);
@@ -203,8 +202,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
     if (relu) {
       const f32x4 yy = reinterpret_cast<const f32x4*>(y)[i];
-      g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f;
-      g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
+      g = relu_mask(g, yy);
     }
     f32x4 o;
 #pragma unroll

@@ -171,7 +171,7 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, training, momentu
 
 class _BnReluPoolFn(Function):
     """The stem's BatchNorm (batch statistics from the convolution epilogue's records) + ReLU + MaxPool2d(3, 2, 1) as
-    one pass each way (csrc/bn.hip: bn_relu_pool_fwd_kernel): the normalised full-resolution map and its gradient are
+    one pass each way (csrc/bn_pool.hip: bn_relu_pool_fwd_kernel): the normalised full-resolution map and its gradient are
     never written.  Replaces bn1 / relu / maxpool of reference ever/module/_resnets.py:150-153."""
 
     @staticmethod

@@ -425,7 +425,7 @@ def bn_relu_dot(z, bn, conv):
     k, c = conv.weight.shape[0], z.shape[1]
     if (parts is None or parts[1] <= 0 or k > 16 or c % 4 or c > 1024 or tuple(conv.weight.shape[2:]) != (1, 1)
             or conv.weight.shape[1] != c or (c > 256 and k > 4) or 16 * (4 + k) * c > 65536):
-        return None      # (the kernel's register / LDS budget: csrc/bn.hip evk_bn_relu_dot_bwd)
+        return None      # (the kernel's register / LDS budget: csrc/bn_dot.hip evk_bn_relu_dot_bwd)
     del z._evk_bn_parts
     weight_planes.note_running_stats_changed()
     if torch.is_grad_enabled():

@@ -1,5 +1,5 @@
-"""The BatchNorm family (csrc/bn.hip) at its plan, channel and map-shape edges, through the C-ABI, against float64 computed on
-the CPU from the same fp32 inputs.
+"""The BatchNorm family (csrc/bn.hip, bn_pool.hip, bn_dot.hip) at its plan, channel and map-shape edges, through the C-ABI,
+against float64 computed on the CPU from the same fp32 inputs.
 
 Shapes are picked WITH evk_bn_plan: a case names the edges it exists for (`want`) and fails with "no longer covers" when a
 retuned plan takes one away; the last test asserts the union.  Every output and the workspace hold NaN before a launch and are

@@ -1,4 +1,4 @@
-"""Properties of the BatchNorm reduce plan (csrc/bn.hip: bn_plan), asked of the library on the host through evk_bn_plan — the
+"""Properties of the BatchNorm reduce plan (csrc/bn_common.hpp: bn_plan), asked of the library on the host through evk_bn_plan — the
 same function the launchers call, no Python copy: no workgroup without rows, no row without a workgroup, a workgroup's rows a
 whole number of thread-rows, the caps, the same for the pool backward's quads, and a workspace that holds all of it."""
 import ctypes
@@ -54,7 +54,8 @@ def _check(t, kind, lib):
     q = rows // 4
     qs = np.maximum(qpb, 1)
     bad(np.where(has_q, (qpb % rl == 0) & ((qn - 1) * qs < q) & (q <= qn * qs) & (qn <= CAP[POOL]), True), 'quad cover')
-    # the workspace: partial records [nblk][2][C], 8 C coefficients, records of maxima [nblk][2][C] (packed dx)
+    # the workspace (csrc/bn_common.hpp: BnWorkspace): partial records [nblk][2][C], 8 C coefficients, records of maxima
+    # [nblk][2][C] (packed dx)
     need = (2 * np.maximum(nblk, qn) * 2 * c + 8 * c) * 4
     for cc in np.unique(c):
         m = c == cc

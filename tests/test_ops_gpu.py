@@ -499,7 +499,7 @@ def test_batchnorm_statistics_from_the_conv_epilogue(cuda, case):
 
 @pytest.mark.parametrize('shape', [(2, 64, 32, 48), (1, 64, 30, 34), (3, 32, 16, 16)])
 def test_stem_batchnorm_relu_maxpool_fused_equals_separate_passes(cuda, shape):
-    """BatchNorm + ReLU + MaxPool2d(3, 2, 1) of the stem as one pass each way (csrc/bn.hip) against the separate passes
+    """BatchNorm + ReLU + MaxPool2d(3, 2, 1) of the stem as one pass each way (csrc/bn_pool.hip) against the separate passes
     and against torch in float64: pooled map, the gradient of the convolution output, dgamma, dbeta."""
     from ever_amd.hip import functional as F
     import torch.nn.functional as TF
