@@ -133,6 +133,10 @@ SIGNATURES = {
     'evk_subsample2_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_upsample_bilinear_fwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_upsample_bilinear_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_upsample_bilinear_slice_fwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_upsample_bilinear_slice_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_hr_fuse_fwd': (c_int, [P, P, P, c_i32, P, P, P, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_hr_fuse_bwd': (c_int, [P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_gap_fwd': (c_int, [P, P, c_i32, c_i32, c_i32, P]),
     'evk_gap_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, P]),
     'evk_relation_fwd': (c_int, [P, P, P, P, P, c_i32, c_i32, c_i32, P]),

@@ -111,4 +111,28 @@ __device__ __forceinline__ void relu_bits_store(uint32_t* __restrict__ bits, siz
         relu_u32x4{(uint32_t)(b0 >> 32), (uint32_t)(b1 >> 32), (uint32_t)(b2 >> 32), (uint32_t)(b3 >> 32)};
 }
 
+
+// max|v| of what a workgroup wrote into slot (workgroup & 63) of the output's operand-scale buffer (64 slots 32 words
+// apart, zero on entry; include/ever_hip.h: evk_absmax) — one atomic per wave, as the BatchNorm and convolution epilogues
+__device__ __forceinline__ uint32_t abs4_bits(uint32_t m, const f32x4 v) {
+  // by value into floats first: __builtin_bit_cast on a vector-element lvalue (v.y) reads element 0 with this compiler
+  const float x = v.x, y = v.y, z = v.z, w = v.w;
+  m = max(m, __float_as_uint(x) & 0x7fffffffu); m = max(m, __float_as_uint(y) & 0x7fffffffu);
+  m = max(m, __float_as_uint(z) & 0x7fffffffu); m = max(m, __float_as_uint(w) & 0x7fffffffu);
+  return m;
+}
+__device__ __forceinline__ void commit_absmax(uint32_t* __restrict__ slots, uint32_t m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(&slots[(blockIdx.x & 63) * 32], m);
+}
+
+// Grid of the streaming kernels (csrc/pointwise.hip, csrc/hr_fuse.hip): one element per thread (their grid-stride loops then run once): resident workgroups sweep one contiguous
+// window of HBM in dispatch order, 6.1 TB/s for 1R+1W on 268 MB against 5.1 for 4096 grid-striding workgroups
+// (tools/probes/copy_patterns.hip).
+static inline int grid_for(size_t n, int per_block = 256, int cap = 1 << 24) {
+  size_t b = (n + per_block - 1) / per_block;
+  return (int)(b > (size_t)cap ? cap : (b < 1 ? 1 : b));
+}
+
 }  // namespace evk

@@ -9,29 +9,6 @@
 
 namespace evk {
 
-// max|v| of what a workgroup wrote into slot (workgroup & 63) of the output's operand-scale buffer (64 slots 32 words
-// apart, zero on entry; include/ever_hip.h: evk_absmax) — one atomic per wave, as the BatchNorm and convolution epilogues
-__device__ __forceinline__ uint32_t abs4_bits(uint32_t m, const f32x4 v) {
-  // by value into floats first: __builtin_bit_cast on a vector-element lvalue (v.y) reads element 0 with this compiler
-  const float x = v.x, y = v.y, z = v.z, w = v.w;
-  m = max(m, __float_as_uint(x) & 0x7fffffffu); m = max(m, __float_as_uint(y) & 0x7fffffffu);
-  m = max(m, __float_as_uint(z) & 0x7fffffffu); m = max(m, __float_as_uint(w) & 0x7fffffffu);
-  return m;
-}
-__device__ __forceinline__ void commit_absmax(uint32_t* __restrict__ slots, uint32_t m) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(&slots[(blockIdx.x & 63) * 32], m);
-}
-
-// One element per thread (the grid-stride loops below then run once): resident workgroups sweep one contiguous
-// window of HBM in dispatch order, 6.1 TB/s for 1R+1W on 268 MB against 5.1 for 4096 grid-striding workgroups
-// (tools/probes/copy_patterns.hip).
-static inline int grid_for(size_t n, int per_block = 256, int cap = 1 << 24) {
-  size_t b = (n + per_block - 1) / per_block;
-  return (int)(b > (size_t)cap ? cap : (b < 1 ? 1 : b));
-}
-
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_d(float x) {
@@ -289,7 +266,9 @@ __global__ __launch_bounds__(256) void subsample2_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
-// Bilinear, align_corners=True (nn.UpsamplingBilinear2d).  Index math follows aten's
+// Bilinear, align_corners=True (nn.UpsamplingBilinear2d).  Cy is the pixel stride of the OUTPUT-sized map (y in the forward,
+// dy in the backward): C for a dense map, Ctot when it is a channel slice of a [N,Ho,Wo,Ctot] concat buffer
+// (evk_upsample_bilinear_slice_*: the pointer is then advanced to the slice's first channel).  Index math follows aten's
 // upsample_bilinear2d: scale = (in-1)/(out-1) in float, src = scale*dst, i0 = (int)src,
 // i1 = i0 + (i0 < in-1), l1 = src - i0, l0 = 1 - l1.
 __device__ __forceinline__ void bl_coord(int o, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
@@ -303,12 +282,13 @@ __device__ __forceinline__ void bl_coord(int o, float scale, int in, int& i0, in
 
 template <int VEC>
 __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int N,
-                                                           int Hi, int Wi, int Ho, int Wo, int C, float sy, float sx) {
+                                                           int Hi, int Wi, int Ho, int Wo, int C, int Cy, float sy, float sx) {
   const int cv = C / VEC;
   const size_t total = (size_t)N * Ho * Wo * cv;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int cb = (int)(i % cv);
     size_t pix = i / cv;
+    float* o = y + pix * Cy + cb * VEC;
     const int ox = (int)(pix % Wo);
     pix /= Wo;
     const int oy = (int)(pix % Ho);
@@ -323,9 +303,9 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restri
     if (VEC == 4) {
       const f32x4 v00 = *reinterpret_cast<const f32x4*>(b + o00), v01 = *reinterpret_cast<const f32x4*>(b + o01);
       const f32x4 v10 = *reinterpret_cast<const f32x4*>(b + o10), v11 = *reinterpret_cast<const f32x4*>(b + o11);
-      *reinterpret_cast<f32x4*>(y + i * 4) = hy0 * (wx0 * v00 + wx1 * v01) + hy1 * (wx0 * v10 + wx1 * v11);
+      *reinterpret_cast<f32x4*>(o) = hy0 * (wx0 * v00 + wx1 * v01) + hy1 * (wx0 * v10 + wx1 * v11);
     } else {
-      y[i] = hy0 * (wx0 * b[o00] + wx1 * b[o01]) + hy1 * (wx0 * b[o10] + wx1 * b[o11]);
+      *o = hy0 * (wx0 * b[o00] + wx1 * b[o01]) + hy1 * (wx0 * b[o10] + wx1 * b[o11]);
     }
   }
 }
@@ -335,7 +315,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restri
 // src in (i-1, i+1)  <=>  o in ((i-1)/scale, (i+1)/scale), widened by one for float rounding.
 template <int VEC>
 __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int N,
-                                                           int Hi, int Wi, int Ho, int Wo, int C, float sy, float sx,
+                                                           int Hi, int Wi, int Ho, int Wo, int C, int Cy, float sy, float sx,
                                                            float isy, float isx) {
   const int cv = C / VEC;
   const size_t total = (size_t)N * Hi * Wi * cv;
@@ -368,7 +348,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
         if (x0 == ix) wx += wx0;
         if (x1 == ix) wx += wx1;
         if (wx == 0.f) continue;
-        const size_t o = (((size_t)n * Ho + oy) * Wo + ox) * C + cb * VEC;
+        const size_t o = (((size_t)n * Ho + oy) * Wo + ox) * Cy + cb * VEC;
         if (VEC == 4) acc4 += (wy * wx) * *reinterpret_cast<const f32x4*>(dy + o);
         else acc1 += (wy * wx) * dy[o];
       }
@@ -393,8 +373,8 @@ constexpr int kTileR = 4, kTileC = 16;
 // takes two pixels side by side there (the per-pixel arithmetic is then per half-wave, on the vector unit)
 template <int LPP>
 __global__ __launch_bounds__(256) void bilinear_fwd_tile_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                int Hi, int Wi, int Ho, int Wo, int C, float sy,
-                                                                float sx, int patch_cols) {
+                                                                int Hi, int Wi, int Ho, int Wo, int C, int Cy,
+                                                                float sy, float sx, int patch_cols) {
   extern __shared__ __attribute__((aligned(16))) float patch[];  // [rows][patch_cols][C]
   constexpr int PPW = 64 / LPP;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
@@ -424,7 +404,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_tile_kernel(const float* __r
   bl_coord(oy, sy, Hi, y0, y1, hy0, hy1);
   const float* r0 = patch + (size_t)(y0 - ylo) * patch_cols * C;
   const float* r1 = patch + (size_t)(y1 - ylo) * patch_cols * C;
-  float* o = y + (((size_t)n * Ho + oy) * Wo + ox0) * C;
+  float* o = y + (((size_t)n * Ho + oy) * Wo + ox0) * Cy;
   for (int j = sub; j <= ox_last - ox0; j += PPW) {
     int x0, x1;
     float wx0, wx1;
@@ -433,7 +413,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_tile_kernel(const float* __r
     for (int k = cl; k < C; k += LPP * 4) {
       const f32x4 v00 = *reinterpret_cast<const f32x4*>(r0 + c0 + k), v01 = *reinterpret_cast<const f32x4*>(r0 + c1 + k);
       const f32x4 v10 = *reinterpret_cast<const f32x4*>(r1 + c0 + k), v11 = *reinterpret_cast<const f32x4*>(r1 + c1 + k);
-      *reinterpret_cast<f32x4*>(o + (size_t)j * C + k) = hy0 * (wx0 * v00 + wx1 * v01) + hy1 * (wx0 * v10 + wx1 * v11);
+      *reinterpret_cast<f32x4*>(o + (size_t)j * Cy + k) = hy0 * (wx0 * v00 + wx1 * v01) + hy1 * (wx0 * v10 + wx1 * v11);
     }
   }
 }
@@ -451,7 +431,7 @@ __device__ __forceinline__ float bl_adjoint_weight(int o, int o_hi, float scale,
 
 __global__ __launch_bounds__(256) void bilinear_bwd_wave_kernel(const float* __restrict__ dy, float* __restrict__ dx,
                                                                 int npix, FastDiv fdWi, FastDiv fdHi, int Ho, int Wo,
-                                                                int C, float sy, float sx, float isy, float isx) {
+                                                                int C, int Cy, float sy, float sx, float isy, float isx) {
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   const int pix = xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;   // see bilinear_fwd_wave_kernel
   if (pix >= npix) return;
@@ -469,7 +449,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_wave_kernel(const float* __r
   const float wxv = bl_adjoint_weight(ox_lo + j, ox_hi, sx, Wi, (int)ix);
   uint32_t my = (uint32_t)(__ballot(wyv != 0.f) & 0xffffull);
   const uint32_t mx = (uint32_t)(__ballot(wxv != 0.f) & 0xffffull);
-  const float* b = dy + (size_t)n * Ho * Wo * C;
+  const float* b = dy + (size_t)n * Ho * Wo * Cy;
   float* o = dx + (size_t)pix * C;
   f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   // same candidate order (oy ascending, then ox ascending) and weight arithmetic as bilinear_bwd_kernel
@@ -477,14 +457,14 @@ __global__ __launch_bounds__(256) void bilinear_bwd_wave_kernel(const float* __r
     const int jy = __builtin_ctz(my);
     my &= my - 1;
     const float wy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wyv), jy));
-    const float* row = b + (size_t)(oy_lo + jy) * Wo * C;
+    const float* row = b + (size_t)(oy_lo + jy) * Wo * Cy;
     uint32_t m = mx;
     while (m) {
       const int jx = __builtin_ctz(m);
       m &= m - 1;
       const float wx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wxv), jx));
       const float w = wy * wx;
-      const float* src = row + (size_t)(ox_lo + jx) * C + lane * 4;
+      const float* src = row + (size_t)(ox_lo + jx) * Cy + lane * 4;
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (lane * 4 + 256 * k < C) acc[k] += w * *reinterpret_cast<const f32x4*>(src + 256 * k);
@@ -948,15 +928,14 @@ extern "C" int evk_subsample2_bwd(const float* dy, float* dx, int32_t N, int32_t
 
 static inline float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
-extern "C" int evk_upsample_bilinear_fwd(const float* x, float* y, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,
-                                         int32_t Wo, int32_t C, void* stream) {
-  EVK_REQUIRE(x && y && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, EVK_E_INVALID,
-              "bilinear_fwd: bad argument");
+// y / dy: the output-sized map's first channel of this call, Cy its pixel stride (C when dense)
+static int bilinear_fwd_launch(const float* x, float* y, int N, int Hi, int Wi, int Ho, int Wo, int C, int Cy, bool vec,
+                               void* stream) {
   const float sy = ac_scale(Hi, Ho), sx = ac_scale(Wi, Wo);
   // patch of one kTileR x kTileC output tile: rows/cols <= floor((tile - 1) * scale) + 3 (first i0 .. last i1)
   const int prow = (int)((kTileR - 1) * sy) + 3, pcol = (int)((kTileC - 1) * sx) + 3;
   const size_t patch_bytes = (size_t)prow * pcol * C * sizeof(float);
-  if (C % 4 == 0 && C >= 128 && patch_bytes <= 64 * 1024 && N <= 65535 && (Ho + kTileR - 1) / kTileR <= 65535) {
+  if (vec && C >= 128 && patch_bytes <= 64 * 1024 && N <= 65535 && (Ho + kTileR - 1) / kTileR <= 65535) {
     static PerDeviceOnce attr_once;
     if (attr_once.first()) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bilinear_fwd_tile_kernel<64>),
@@ -967,40 +946,64 @@ extern "C" int evk_upsample_bilinear_fwd(const float* x, float* y, int32_t N, in
     const dim3 grid((Wo + kTileC - 1) / kTileC, (Ho + kTileR - 1) / kTileR, N);
     if (C <= 128)
       hipLaunchKernelGGL(bilinear_fwd_tile_kernel<32>, grid, dim3(256), patch_bytes, (hipStream_t)stream, x, y, Hi, Wi, Ho, Wo,
-                         C, sy, sx, pcol);
+                         C, Cy, sy, sx, pcol);
     else
       hipLaunchKernelGGL(bilinear_fwd_tile_kernel<64>, grid, dim3(256), patch_bytes, (hipStream_t)stream, x, y, Hi, Wi, Ho, Wo,
-                         C, sy, sx, pcol);
+                         C, Cy, sy, sx, pcol);
   }
-  else if (C % 4 == 0)
+  else if (vec)
     hipLaunchKernelGGL(bilinear_fwd_kernel<4>, dim3(grid_for((size_t)N * Ho * Wo * (C / 4))), dim3(256), 0,
-                       (hipStream_t)stream, x, y, N, Hi, Wi, Ho, Wo, C, sy, sx);
+                       (hipStream_t)stream, x, y, N, Hi, Wi, Ho, Wo, C, Cy, sy, sx);
   else
     hipLaunchKernelGGL(bilinear_fwd_kernel<1>, dim3(grid_for((size_t)N * Ho * Wo * C)), dim3(256), 0,
-                       (hipStream_t)stream, x, y, N, Hi, Wi, Ho, Wo, C, sy, sx);
+                       (hipStream_t)stream, x, y, N, Hi, Wi, Ho, Wo, C, Cy, sy, sx);
   return check_launch("bilinear_fwd");
 }
-extern "C" int evk_upsample_bilinear_bwd(const float* dy, float* dx, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,
-                                         int32_t Wo, int32_t C, void* stream) {
-  EVK_REQUIRE(dy && dx && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, EVK_E_INVALID,
-              "bilinear_bwd: bad argument");
+static int bilinear_bwd_launch(const float* dy, float* dx, int N, int Hi, int Wi, int Ho, int Wo, int C, int Cy, bool vec,
+                               void* stream) {
   const float sy = ac_scale(Hi, Ho), sx = ac_scale(Wi, Wo);
   // inverse scales for the candidate range; in == 1 => every output maps to input 0
   const float isy = sy > 0.f ? 1.f / sy : (float)Ho, isx = sx > 0.f ? 1.f / sx : (float)Wo;
   const long long npix_i = (long long)N * Hi * Wi;
   // candidate range per axis: ceil((i+1)/s)+1 - (floor((i-1)/s)-1) + 1 <= 2/s + 5; the wave kernel holds 16 per axis
   const bool narrow = 2.f * isy + 5.f <= 16.f && 2.f * isx + 5.f <= 16.f && Hi > 1 && Wi > 1;
-  if (C % 4 == 0 && C >= 128 && C <= 1024 && narrow && npix_i < 0x7fffffffLL)
+  if (vec && C >= 128 && C <= 1024 && narrow && npix_i < 0x7fffffffLL)
     hipLaunchKernelGGL(bilinear_bwd_wave_kernel, dim3((unsigned)((npix_i + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       dy, dx, (int)npix_i, make_fastdiv((uint32_t)Wi), make_fastdiv((uint32_t)Hi), Ho, Wo, C, sy, sx,
+                       dy, dx, (int)npix_i, make_fastdiv((uint32_t)Wi), make_fastdiv((uint32_t)Hi), Ho, Wo, C, Cy, sy, sx,
                        isy, isx);
-  else if (C % 4 == 0)
+  else if (vec)
     hipLaunchKernelGGL(bilinear_bwd_kernel<4>, dim3(grid_for((size_t)N * Hi * Wi * (C / 4))), dim3(256), 0,
-                       (hipStream_t)stream, dy, dx, N, Hi, Wi, Ho, Wo, C, sy, sx, isy, isx);
+                       (hipStream_t)stream, dy, dx, N, Hi, Wi, Ho, Wo, C, Cy, sy, sx, isy, isx);
   else
     hipLaunchKernelGGL(bilinear_bwd_kernel<1>, dim3(grid_for((size_t)N * Hi * Wi * C)), dim3(256), 0,
-                       (hipStream_t)stream, dy, dx, N, Hi, Wi, Ho, Wo, C, sy, sx, isy, isx);
+                       (hipStream_t)stream, dy, dx, N, Hi, Wi, Ho, Wo, C, Cy, sy, sx, isy, isx);
   return check_launch("bilinear_bwd");
+}
+
+extern "C" int evk_upsample_bilinear_fwd(const float* x, float* y, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,
+                                         int32_t Wo, int32_t C, void* stream) {
+  EVK_REQUIRE(x && y && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, EVK_E_INVALID,
+              "bilinear_fwd: bad argument");
+  return bilinear_fwd_launch(x, y, N, Hi, Wi, Ho, Wo, C, C, C % 4 == 0, stream);
+}
+extern "C" int evk_upsample_bilinear_bwd(const float* dy, float* dx, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,
+                                         int32_t Wo, int32_t C, void* stream) {
+  EVK_REQUIRE(dy && dx && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, EVK_E_INVALID,
+              "bilinear_bwd: bad argument");
+  return bilinear_bwd_launch(dy, dx, N, Hi, Wi, Ho, Wo, C, C, C % 4 == 0, stream);
+}
+// The same kernels on a channel slice of the output-sized map: 16-byte accesses need the slice and the pixel stride aligned
+extern "C" int evk_upsample_bilinear_slice_fwd(const float* x, float* y, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,
+                                               int32_t Wo, int32_t C, int32_t c0, int32_t Ctot, void* stream) {
+  EVK_REQUIRE(x && y && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && c0 >= 0 && (int64_t)c0 + C <= Ctot,
+              EVK_E_INVALID, "bilinear_slice_fwd: bad argument (need 0 <= c0, c0 + C <= Ctot)");
+  return bilinear_fwd_launch(x, y + c0, N, Hi, Wi, Ho, Wo, C, Ctot, C % 4 == 0 && c0 % 4 == 0 && Ctot % 4 == 0, stream);
+}
+extern "C" int evk_upsample_bilinear_slice_bwd(const float* dy, float* dx, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,
+                                               int32_t Wo, int32_t C, int32_t c0, int32_t Ctot, void* stream) {
+  EVK_REQUIRE(dy && dx && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && c0 >= 0 && (int64_t)c0 + C <= Ctot,
+              EVK_E_INVALID, "bilinear_slice_bwd: bad argument (need 0 <= c0, c0 + C <= Ctot)");
+  return bilinear_bwd_launch(dy + c0, dx, N, Hi, Wi, Ho, Wo, C, Ctot, C % 4 == 0 && c0 % 4 == 0 && Ctot % 4 == 0, stream);
 }
 
 extern "C" int evk_gap_fwd(const float* x, float* y, int32_t N, int32_t HW, int32_t C, void* stream) {

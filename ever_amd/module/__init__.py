@@ -6,6 +6,10 @@ from .deeplabv3p_head import Deeplabv3pDecoder, Deeplabv3pHead
 from .farseg import FarSeg, FarSegPP
 from .fpn import FPN, AssymetricDecoder
 from .freenet import FreeNet
+from .hrnet import HRNetEncoder
+from .hrnet_head import HRNetHead, SimpleFusion
+from .hrnet_seg import HRNetSeg
+from ._hrnet import HighResolutionModule, HighResolutionNet
 from .fs_relation import FarSegHead, FarSegPPHead, FSRelation, FSRelationV2
 from .layers import (AdaptiveAvgPool2d, BatchNorm2d, Conv2d, ConvTranspose2d, HipSequential, MaxPool2d, ReLU, UpsamplingBilinear2d,
                      to_hip)
@@ -16,4 +20,5 @@ __all__ = ['ResNetEncoder', 'FPN', 'AssymetricDecoder', 'FSRelation', 'FSRelatio
            'Bf16compatible', 'ConvUpsampling', 'Conv2d', 'ConvTranspose2d', 'BatchNorm2d', 'ReLU', 'MaxPool2d', 'UpsamplingBilinear2d',
            'AdaptiveAvgPool2d', 'HipSequential', 'to_hip', 'loss',
            'DepthwiseConv2d', 'SeparableConv2d', 'SeparableConvBlock', 'PoolBlock', 'AtrousSpatialPyramidPool', 'ASPPHead',
-           'Deeplabv3pDecoder', 'Deeplabv3pHead', 'DeepLabV3Plus']
+           'Deeplabv3pDecoder', 'Deeplabv3pHead', 'DeepLabV3Plus',
+           'HighResolutionModule', 'HighResolutionNet', 'HRNetEncoder', 'SimpleFusion', 'HRNetHead', 'HRNetSeg']

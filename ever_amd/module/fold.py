@@ -62,7 +62,7 @@ def _fold_pair(conv, bn):
 
 def fold_batchnorm(model):
     """Attach folded parameters to every Conv2d that is directly followed by a BatchNorm2d at a known call site
-    (ResNet stem / blocks / down-sampling branches, conv-BN neighbours inside Sequential containers) and switch the
+    (ResNet stem / blocks / down-sampling branches, HRNet's stem, conv-BN neighbours inside Sequential containers) and switch the
     model to eval mode.  Call again after loading new weights."""
     from . import _resnets
     from .layers import Conv2d
@@ -88,6 +88,9 @@ def fold_batchnorm(model):
                 pair(m.conv3, m.bn3)
             if m.downsample is not None:
                 pair(m.downsample[0], m.downsample[1])
+        if hasattr(m, 'conv_bn_pairs'):      # a body that keeps convolution / BatchNorm neighbours as plain attributes (HRNet's stem)
+            for conv, bn in m.conv_bn_pairs():
+                pair(conv, bn)
         if isinstance(m, torch.nn.Sequential):
             kids = list(m)
             for a, b in zip(kids, kids[1:]):

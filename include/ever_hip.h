@@ -450,6 +450,34 @@ int evk_upsample_bilinear_fwd(const float* x, float* y, int32_t N, int32_t Hi, i
                               int32_t Ho, int32_t Wo, int32_t C, void* stream);
 int evk_upsample_bilinear_bwd(const float* dy, float* dx, int32_t N, int32_t Hi, int32_t Wi,
                               int32_t Ho, int32_t Wo, int32_t C, void* stream);
+/* The same resampling with y / dy the channel slice [c0, c0 + C) of a [N,Ho,Wo,Ctot] map (the same kernels, another pixel
+ * stride: bit-identical to the dense calls) — hrnet_head.py:17-25 (SimpleFusion: `torch.cat` of the up-sampled branches):
+ * every source is written straight into its place in the concat buffer, and its gradient read straight out of the buffer's.
+ * Equal sizes copy.  The other channels of y are not touched.  -1 unless 0 <= c0 and c0 + C <= Ctot. */
+int evk_upsample_bilinear_slice_fwd(const float* x, float* y, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,
+                                    int32_t Wo, int32_t C, int32_t c0, int32_t Ctot, void* stream);
+int evk_upsample_bilinear_slice_bwd(const float* dy, float* dx, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,
+                                    int32_t Wo, int32_t C, int32_t c0, int32_t Ctot, void* stream);
+
+/* The exchange that ends a HighResolutionModule — _hrnet.py:377-397: y = ReLU(((t0 + t1) + t2) + t3) over 1 to 4 terms
+ * (csrc/hr_fuse.hip).  Term k is the map terms[k] = [N, H >> s, W >> s, C] with s = shifts[k] in 0..3, read at output pixel
+ * (y, x) as v = terms[k][n, y >> s, x >> s, :] (nearest up-sampling by 2^s); with scale_shifts[k] != NULL ([2][C]: a BatchNorm
+ * as evk_bn_finalize_parts leaves it) the term is fma(v, scale, shift), else v.  The three arrays are HOST arrays of nterms
+ * entries read during the call.  relu_bits: evk_relu_bits_bytes(N * H * W * C) bytes, bit = (y > 0), layout in
+ * csrc/common.hpp; y_absmax (may be NULL): as out_absmax of evk_upsample_nearest2x_add_fwd.
+ * -1: null pointer or non-positive size.  -2 (with a text): C % 4 != 0, nterms outside 1..4, a shift outside 0..3, H or W
+ * not a multiple of 2^(largest shift), 2^31 or more 16-byte elements. */
+int evk_hr_fuse_fwd(const float* const* terms, const int32_t* shifts, const float* const* scale_shifts, int32_t nterms,
+                    float* y, uint32_t* relu_bits, uint32_t* y_absmax, int32_t N, int32_t H, int32_t W, int32_t C,
+                    void* stream);
+/* Its backward, one read of dy [N,H,W,C] and the bits; every output may be NULL (not all): dmasked = dy where the bit is set
+ * (the gradient of a same-resolution term: an identity term takes it as it is, a BatchNorm term runs evk_bn_bwd_bits
+ * without EVK_BN_RELU on (dy, bits) and needs no dmasked), dpooled_s [N, H >> s, W >> s, C] = the sum of the masked dy over
+ * each 2^s x 2^s block (the gradient of a term with shift s: a BatchNorm term runs evk_bn_bwd on it).  H and W must be
+ * multiples of 2^(largest requested s).  One owner per output element and a fixed order of summation: no atomics, the same
+ * bits every run.  Error codes as the forward. */
+int evk_hr_fuse_bwd(const float* dy, const uint32_t* relu_bits, float* dmasked, float* dpooled1, float* dpooled2,
+                    float* dpooled3, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 
 /* F.adaptive_avg_pool2d(x, 1) — fs_relation.py:177. x: [N,HW,C] -> y: [N,C]. */
 int evk_gap_fwd(const float* x, float* y, int32_t N, int32_t HW, int32_t C, void* stream);
