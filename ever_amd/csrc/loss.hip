@@ -10,6 +10,8 @@ namespace evk {
 
 constexpr int kLossBlocks = 2048;   // 256 left the 4-million-pixel losses on a quarter of the chip (62 us for 50 MB)
 constexpr int kMaxClasses = 64;
+constexpr int kDiceLdsBytes = 64 * 1024;
+constexpr int kDiceMaxClasses = kDiceLdsBytes / (256 * 2 * (int)sizeof(double));  // 16: [256][2C] doubles of the softmax path
 
 static inline int loss_grid(int64_t npix) {
   int64_t b = (npix + 2047) / 2048;   // >= 8 pixels per thread
@@ -126,9 +128,9 @@ __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restri
       for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
       float se = 0.f;
       for (int c = 0; c < C; ++c) se += expf(x[c] - m);
-      const float lse = m + logf(se);
+      const float ls = logf(se);  // log p_c = (x_c - m) - ls: no rounding at the size of m (m + ls would lose a small loss)
       for (int c = 0; c < C; ++c) {
-        const float p = expf(x[c] - lse);  // reference: log_softmax(dim=1).exp()
+        const float p = expf((x[c] - m) - ls);  // reference: log_softmax(dim=1).exp()
         const float y = (t == c) ? 1.f : 0.f;
         mine[c] += (double)(p * y);
         mine[C + c] += (double)p + (double)y;
@@ -193,15 +195,15 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
       for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
       float se = 0.f;
       for (int c = 0; c < C; ++c) se += expf(x[c] - m);
-      const float lse = m + logf(se);
+      const float ls = logf(se);
       float dotgp = 0.f;
       for (int c = 0; c < C; ++c) {
-        const float p = expf(x[c] - lse);
+        const float p = expf((x[c] - m) - ls);
         const float g = sa[c] * ((t == c) ? 1.f : 0.f) + sb[c];
         dotgp += g * p;
       }
       for (int c = 0; c < C; ++c) {
-        const float p = expf(x[c] - lse);
+        const float p = expf((x[c] - m) - ls);
         const float g = sa[c] * ((t == c) ? 1.f : 0.f) + sb[c];
         const float v = p * (g - dotgp);
         d[c] = accumulate ? d[c] + v : v;
@@ -225,13 +227,13 @@ __global__ __launch_bounds__(256) void ce_partial_kernel(const float* __restrict
     float se = 0.f, sx = 0.f;
     for (int c = 0; c < C; ++c) {
       se += expf(x[c] - m);
-      sx += x[c];
+      sx += x[c] - m;
     }
-    const float lse = m + logf(se);
-    const float xt = (t >= 0 && t < C) ? x[t] : 0.f;
-    v[0] += (double)(lse - xt);
+    const float ls = logf(se);
+    const float nll = (t >= 0 && t < C) ? ls - (x[t] - m) : m + ls;
+    v[0] += (double)nll;
     v[1] += 1.0;
-    v[2] += (double)((float)C * lse - sx);
+    v[2] += (double)((float)C * ls - sx);
   }
   block_reduce_store<3>(v, stats + 3 + (size_t)blockIdx.x * 3);
 }
@@ -261,9 +263,9 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
     for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(x[c] - m);
-    const float lse = m + logf(se);
+    const float ls = logf(se);
     for (int c = 0; c < C; ++c) {
-      const float p = expf(x[c] - lse);
+      const float p = expf((x[c] - m) - ls);
       const float v = k1 * (p - ((t == c) ? 1.f : 0.f)) + k2 * ((float)C * p - 1.f);
       d[c] = accumulate ? d[c] + v : v;
     }
@@ -284,9 +286,9 @@ __global__ __launch_bounds__(256) void soft_ce_partial_kernel(const float* __res
     for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(x[c] - m);
-    const float lse = m + logf(se);
+    const float ls = logf(se);
     float acc = 0.f;
-    for (int c = 0; c < C; ++c) acc += t[c] * (lse - x[c]);
+    for (int c = 0; c < C; ++c) acc += t[c] * (ls - (x[c] - m));
     v[0] += (double)acc;
   }
   block_reduce_store<1>(v, stats + 1 + (size_t)blockIdx.x);
@@ -310,8 +312,8 @@ __global__ __launch_bounds__(256) void soft_ce_bwd_kernel(const float* __restric
       se += expf(x[c] - m);
       ts += t[c];
     }
-    const float lse = m + logf(se);
-    for (int c = 0; c < C; ++c) d[c] = k * (expf(x[c] - lse) * ts - t[c]);
+    const float ls = logf(se);
+    for (int c = 0; c < C; ++c) d[c] = k * (expf((x[c] - m) - ls) * ts - t[c]);
   }
 }
 
@@ -379,15 +381,16 @@ extern "C" int evk_bce_bwd(const float* logits, const int64_t* labels, int64_t n
 
 extern "C" int evk_dice_stats(const float* logits, const int64_t* labels, int64_t npix, int32_t C, int64_t ignore_index,
                               double* stats, void* stream) {
-  EVK_REQUIRE(logits && labels && stats && npix > 0 && C >= 1 && C <= kMaxClasses, EVK_E_INVALID,
-              "dice_stats: bad argument (1 <= C <= %d)", kMaxClasses);
+  EVK_REQUIRE(logits && labels && stats && npix > 0, EVK_E_INVALID, "dice_stats: bad argument");
+  EVK_REQUIRE(C >= 1 && C <= kDiceMaxClasses, EVK_E_UNSUPPORTED,
+              "dice_stats: C=%d outside [1,%d] (the softmax path keeps 256 x 2C doubles in 64 KiB of LDS)", C,
+              kDiceMaxClasses);
   hipStream_t st = (hipStream_t)stream;
   const int nb = loss_grid(npix);
   if (C == 1) {
     hipLaunchKernelGGL(dice_partial_kernel<1>, dim3(nb), dim3(256), 0, st, logits, labels, npix, C, ignore_index, stats);
   } else {
     const size_t lds = (size_t)256 * 2 * C * sizeof(double);
-    EVK_REQUIRE(lds <= 64 * 1024, EVK_E_UNSUPPORTED, "dice_stats: C=%d too large for the LDS accumulator", C);
     hipLaunchKernelGGL(dice_partial_kernel<0>, dim3(nb), dim3(256), lds, st, logits, labels, npix, C, ignore_index,
                        stats);
   }

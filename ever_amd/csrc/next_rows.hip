@@ -50,9 +50,9 @@ __global__ __launch_bounds__(256) void prob_stats_kernel(const float* __restrict
       for (int c = 1; c < C; ++c) m = fmaxf(m, z[c]);
       float s = 0.f;
       for (int c = 0; c < C; ++c) s += expf(z[c] - m);
-      const float lse = m + logf(s);
+      const float ls = logf(s);  // log p_c = (z_c - m) - ls: no rounding at the size of m
       for (int c = 0; c < C; ++c) {
-        const float p = expf(z[c] - lse);
+        const float p = expf((z[c] - m) - ls);
         sp[c] += (double)p;
         if (t == c) {
           tp[c] += (double)p;
@@ -103,11 +103,11 @@ __global__ __launch_bounds__(256) void prob_stats_bwd_kernel(const float* __rest
       for (int c = 1; c < C; ++c) m = fmaxf(m, z[c]);
       float s = 0.f;
       for (int c = 0; c < C; ++c) s += expf(z[c] - m);
-      const float lse = m + logf(s);
+      const float ls = logf(s);
       float dot = 0.f;
-      for (int c = 0; c < C; ++c) dot += (gsp[c] + (t == c ? gtp[c] : 0.f)) * expf(z[c] - lse);
+      for (int c = 0; c < C; ++c) dot += (gsp[c] + (t == c ? gtp[c] : 0.f)) * expf((z[c] - m) - ls);
       for (int c = 0; c < C; ++c) {
-        const float p = expf(z[c] - lse);
+        const float p = expf((z[c] - m) - ls);
         const float g = p * ((gsp[c] + (t == c ? gtp[c] : 0.f)) - dot);
         d[c] = accumulate ? d[c] + g : g;
       }
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void ce_pixel_kernel(const float* __restrict__
     for (int c = 1; c < C; ++c) m = fmaxf(m, z[c]);
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += expf(z[c] - m);
-    loss[i] = (m + logf(s)) - z[t];
+    loss[i] = logf(s) - (z[t] - m);
   }
 }
 __global__ __launch_bounds__(256) void ce_pixel_bwd_kernel(const float* __restrict__ logits,
@@ -327,8 +327,8 @@ __global__ __launch_bounds__(256) void ce_pixel_bwd_kernel(const float* __restri
     for (int c = 1; c < C; ++c) m = fmaxf(m, z[c]);
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += expf(z[c] - m);
-    const float lse = m + logf(s);
-    for (int c = 0; c < C; ++c) d[c] = g * (expf(z[c] - lse) - (t == c ? 1.f : 0.f));
+    const float ls = logf(s);
+    for (int c = 0; c < C; ++c) d[c] = g * (expf((z[c] - m) - ls) - (t == c ? 1.f : 0.f));
   }
 }
 
@@ -477,6 +477,9 @@ extern "C" int evk_ohem_bwd(const float* losses, int64_t n, void* state, const f
   EVK_REQUIRE(losses && state && dlosses && n > 0, EVK_E_INVALID, "ohem_bwd: bad argument");
   unsigned long long* s = reinterpret_cast<unsigned long long*>(state);
   const double* partial = reinterpret_cast<const double*>(s + 4 + 2048);
+  // the tie counter belongs to one backward pass: a second pass over the same forward (retain_graph) starts from 0 again
+  hipError_t e = hipMemsetAsync(s + 3, 0, sizeof(unsigned long long), (hipStream_t)stream);
+  if (e != hipSuccess) { set_error("ohem_bwd: memset: %s", hipGetErrorString(e)); return EVK_E_LAUNCH; }
   const int64_t b = (n + 255) / 256;
   hipLaunchKernelGGL(ohem_bwd_kernel, dim3((unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b))), dim3(256), 0,
                      (hipStream_t)stream, losses, n, s, partial, grad_scale, dlosses);

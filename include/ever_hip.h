@@ -525,6 +525,7 @@ int evk_bce_bwd_ex(const float* logits, const int64_t* labels, int64_t npix, int
                    const float* grad_scale, float* dlogits, int32_t accumulate, void* stream);
 
 /* dice_loss_with_logits — loss.py:40-75.  C==1: p=sigmoid; C>1: p=softmax, one-hot target.
+ * 1 <= C <= 16: the softmax statistics keep 256 x 2C doubles in 64 KiB of LDS; evk_dice_stats refuses a larger C.
  * stats: double[2*C] = {inter[c], z[c]} (z = sum p + sum y, before smoothing).  In distributed
  * training the caller all-reduces `stats` between evk_dice_stats and evk_dice_finish
  * (loss.py:20-23,46-48). */
