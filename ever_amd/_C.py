@@ -133,6 +133,7 @@ SIGNATURES = {
     'evk_subsample2_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_upsample_bilinear_fwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_upsample_bilinear_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_upsample_bilinear_plan': (c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
     'evk_upsample_bilinear_slice_fwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_upsample_bilinear_slice_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_hr_fuse_fwd': (c_int, [P, P, P, c_i32, P, P, P, c_i32, c_i32, c_i32, c_i32, P]),

@@ -15,6 +15,9 @@ __device__ __forceinline__ float gelu_d(float x) {
   return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * expf(-0.5f * x * x);
 }
 
+// aten's relu is clamp_min(x, 0): -0.0 stays -0.0 (fmaxf gives +0.0 on this hardware).  A NaN becomes 0 here, as under fmaxf.
+__device__ __forceinline__ float relu_f(float x) { return x >= 0.f ? x : 0.f; }
+
 template <int OP>  // 0 relu, 1 relu_bwd, 2 add, 3 scale, 4 a*b*alpha, 5 gelu, 6 gelu_bwd (a = dy, b = x)
 __global__ __launch_bounds__(256) void ew_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                  float* __restrict__ o, size_t n, float alpha) {
@@ -26,7 +29,7 @@ __global__ __launch_bounds__(256) void ew_kernel(const float* __restrict__ a, co
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
     f32x4 v = a4[i];
     if (OP == 0) {
-      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+      v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
     } else if (OP == 1) {  // a = dy, b = y
       const f32x4 y = b4[i];
       v.x = y.x > 0.f ? v.x : 0.f; v.y = y.y > 0.f ? v.y : 0.f;
@@ -48,7 +51,7 @@ __global__ __launch_bounds__(256) void ew_kernel(const float* __restrict__ a, co
   // tail
   for (size_t i = (n4 << 2) + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     float v = a[i];
-    if (OP == 0) v = fmaxf(v, 0.f);
+    if (OP == 0) v = relu_f(v);
     else if (OP == 1) v = b[i] > 0.f ? v : 0.f;
     else if (OP == 2) v += b[i];
     else if (OP == 3) v *= alpha;
@@ -928,14 +931,47 @@ extern "C" int evk_subsample2_bwd(const float* dy, float* dx, int32_t N, int32_t
 
 static inline float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
+// Which kernel a resampling call takes, and the numbers that kernel is launched with.  Pure host arithmetic, shared by the two
+// launchers and evk_upsample_bilinear_plan.  `vec`: 16-byte accesses are legal (C, and for a slice c0 and Ctot, multiples of 4).
+enum BilinearKernel { kBlScalar = 0, kBlVec = 1, kBlTile32 = 2, kBlTile64 = 3, kBlWave = 4 };
+struct BilinearPlan {
+  int kernel;
+  int prow, pcol;        // forward: bound of the input patch one kTileR x kTileC output tile reads (the tile kernels' LDS)
+  size_t patch_bytes;
+  float sy, sx;          // (in - 1) / (out - 1), 0 for a one-pixel output
+  float isy, isx;        // backward: inverse scales of the candidate range (in == 1 => every output maps to input 0)
+};
+static BilinearPlan bilinear_plan(int N, int Hi, int Wi, int Ho, int Wo, int C, bool vec, bool backward) {
+  BilinearPlan pl = {};
+  pl.sy = ac_scale(Hi, Ho);
+  pl.sx = ac_scale(Wi, Wo);
+  pl.kernel = vec ? kBlVec : kBlScalar;
+  if (!backward) {
+    // patch of one kTileR x kTileC output tile: rows/cols <= floor((tile - 1) * scale) + 3 (first i0 .. last i1)
+    pl.prow = (int)((kTileR - 1) * pl.sy) + 3;
+    pl.pcol = (int)((kTileC - 1) * pl.sx) + 3;
+    pl.patch_bytes = (size_t)pl.prow * pl.pcol * C * sizeof(float);
+    if (vec && C >= 128 && pl.patch_bytes <= 64 * 1024 && N <= 65535 && (Ho + kTileR - 1) / kTileR <= 65535)
+      pl.kernel = C <= 128 ? kBlTile32 : kBlTile64;
+  } else {
+    pl.isy = pl.sy > 0.f ? 1.f / pl.sy : (float)Ho;
+    pl.isx = pl.sx > 0.f ? 1.f / pl.sx : (float)Wo;
+    const long long npix_i = (long long)N * Hi * Wi;
+    // candidate range per axis: ceil((i+1)/s)+1 - (floor((i-1)/s)-1) + 1 <= 2/s + 5; the wave kernel holds 16 per axis
+    const bool narrow = 2.f * pl.isy + 5.f <= 16.f && 2.f * pl.isx + 5.f <= 16.f && Hi > 1 && Wi > 1;
+    if (vec && C >= 128 && C <= 1024 && narrow && npix_i < 0x7fffffffLL) pl.kernel = kBlWave;
+  }
+  return pl;
+}
+
 // y / dy: the output-sized map's first channel of this call, Cy its pixel stride (C when dense)
 static int bilinear_fwd_launch(const float* x, float* y, int N, int Hi, int Wi, int Ho, int Wo, int C, int Cy, bool vec,
                                void* stream) {
-  const float sy = ac_scale(Hi, Ho), sx = ac_scale(Wi, Wo);
-  // patch of one kTileR x kTileC output tile: rows/cols <= floor((tile - 1) * scale) + 3 (first i0 .. last i1)
-  const int prow = (int)((kTileR - 1) * sy) + 3, pcol = (int)((kTileC - 1) * sx) + 3;
-  const size_t patch_bytes = (size_t)prow * pcol * C * sizeof(float);
-  if (vec && C >= 128 && patch_bytes <= 64 * 1024 && N <= 65535 && (Ho + kTileR - 1) / kTileR <= 65535) {
+  const BilinearPlan pl = bilinear_plan(N, Hi, Wi, Ho, Wo, C, vec, false);
+  const float sy = pl.sy, sx = pl.sx;
+  const int pcol = pl.pcol;
+  const size_t patch_bytes = pl.patch_bytes;
+  if (pl.kernel == kBlTile32 || pl.kernel == kBlTile64) {
     static PerDeviceOnce attr_once;
     if (attr_once.first()) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bilinear_fwd_tile_kernel<64>),
@@ -944,14 +980,14 @@ static int bilinear_fwd_launch(const float* x, float* y, int N, int Hi, int Wi, 
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     }
     const dim3 grid((Wo + kTileC - 1) / kTileC, (Ho + kTileR - 1) / kTileR, N);
-    if (C <= 128)
+    if (pl.kernel == kBlTile32)
       hipLaunchKernelGGL(bilinear_fwd_tile_kernel<32>, grid, dim3(256), patch_bytes, (hipStream_t)stream, x, y, Hi, Wi, Ho, Wo,
                          C, Cy, sy, sx, pcol);
     else
       hipLaunchKernelGGL(bilinear_fwd_tile_kernel<64>, grid, dim3(256), patch_bytes, (hipStream_t)stream, x, y, Hi, Wi, Ho, Wo,
                          C, Cy, sy, sx, pcol);
   }
-  else if (vec)
+  else if (pl.kernel == kBlVec)
     hipLaunchKernelGGL(bilinear_fwd_kernel<4>, dim3(grid_for((size_t)N * Ho * Wo * (C / 4))), dim3(256), 0,
                        (hipStream_t)stream, x, y, N, Hi, Wi, Ho, Wo, C, Cy, sy, sx);
   else
@@ -961,23 +997,39 @@ static int bilinear_fwd_launch(const float* x, float* y, int N, int Hi, int Wi, 
 }
 static int bilinear_bwd_launch(const float* dy, float* dx, int N, int Hi, int Wi, int Ho, int Wo, int C, int Cy, bool vec,
                                void* stream) {
-  const float sy = ac_scale(Hi, Ho), sx = ac_scale(Wi, Wo);
-  // inverse scales for the candidate range; in == 1 => every output maps to input 0
-  const float isy = sy > 0.f ? 1.f / sy : (float)Ho, isx = sx > 0.f ? 1.f / sx : (float)Wo;
+  const BilinearPlan pl = bilinear_plan(N, Hi, Wi, Ho, Wo, C, vec, true);
+  const float sy = pl.sy, sx = pl.sx, isy = pl.isy, isx = pl.isx;
   const long long npix_i = (long long)N * Hi * Wi;
-  // candidate range per axis: ceil((i+1)/s)+1 - (floor((i-1)/s)-1) + 1 <= 2/s + 5; the wave kernel holds 16 per axis
-  const bool narrow = 2.f * isy + 5.f <= 16.f && 2.f * isx + 5.f <= 16.f && Hi > 1 && Wi > 1;
-  if (vec && C >= 128 && C <= 1024 && narrow && npix_i < 0x7fffffffLL)
+  if (pl.kernel == kBlWave)
     hipLaunchKernelGGL(bilinear_bwd_wave_kernel, dim3((unsigned)((npix_i + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        dy, dx, (int)npix_i, make_fastdiv((uint32_t)Wi), make_fastdiv((uint32_t)Hi), Ho, Wo, C, Cy, sy, sx,
                        isy, isx);
-  else if (vec)
+  else if (pl.kernel == kBlVec)
     hipLaunchKernelGGL(bilinear_bwd_kernel<4>, dim3(grid_for((size_t)N * Hi * Wi * (C / 4))), dim3(256), 0,
                        (hipStream_t)stream, dy, dx, N, Hi, Wi, Ho, Wo, C, Cy, sy, sx, isy, isx);
   else
     hipLaunchKernelGGL(bilinear_bwd_kernel<1>, dim3(grid_for((size_t)N * Hi * Wi * C)), dim3(256), 0,
                        (hipStream_t)stream, dy, dx, N, Hi, Wi, Ho, Wo, C, Cy, sy, sx, isy, isx);
   return check_launch("bilinear_bwd");
+}
+
+// Host only (no launch): the plan of a resampling call.  out[8] = {kernel (0 scalar element, 1 16-byte element, 2 tile with 32
+// lanes per pixel, 3 tile with 64, 4 wave per pixel), patch rows, patch columns, patch bytes (forward; 0 in the backward;
+// saturated at INT32_MAX), bit images of sy, sx, isy, isx as the kernels receive them (isy, isx: 0 in the forward)}
+extern "C" int evk_upsample_bilinear_plan(int32_t N, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t C, int32_t vec,
+                                          int32_t backward, int32_t* out) {
+  EVK_REQUIRE(out && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && (!vec || C % 4 == 0), EVK_E_INVALID,
+              "bilinear_plan: bad argument");
+  const BilinearPlan pl = bilinear_plan(N, Hi, Wi, Ho, Wo, C, vec != 0, backward != 0);
+  out[0] = pl.kernel;
+  out[1] = pl.prow;
+  out[2] = pl.pcol;
+  out[3] = pl.patch_bytes > 0x7fffffffull ? 0x7fffffff : (int32_t)pl.patch_bytes;
+  out[4] = __builtin_bit_cast(int32_t, pl.sy);
+  out[5] = __builtin_bit_cast(int32_t, pl.sx);
+  out[6] = __builtin_bit_cast(int32_t, pl.isy);
+  out[7] = __builtin_bit_cast(int32_t, pl.isx);
+  return EVK_OK;
 }
 
 extern "C" int evk_upsample_bilinear_fwd(const float* x, float* y, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,

@@ -450,6 +450,15 @@ int evk_upsample_bilinear_fwd(const float* x, float* y, int32_t N, int32_t Hi, i
                               int32_t Ho, int32_t Wo, int32_t C, void* stream);
 int evk_upsample_bilinear_bwd(const float* dy, float* dx, int32_t N, int32_t Hi, int32_t Wi,
                               int32_t Ho, int32_t Wo, int32_t C, void* stream);
+/* Host only, no launch: the kernel a resampling call takes and what it is launched with (tests pick their shapes with it).
+ * vec: 16-byte accesses are legal (C % 4 == 0, and for a slice c0 % 4 == 0 and Ctot % 4 == 0); backward: 0 = _fwd, 1 = _bwd.
+ * out[8] = { kernel, patch rows, patch columns, patch bytes, bits of sy, sx, isy, isx }.  kernel: 0 element per thread,
+ * scalar; 1 element per thread, 16-byte; 2 LDS tile, 32 lanes per pixel; 3 LDS tile, 64 lanes per pixel (forward only);
+ * 4 wave per pixel (backward only).  The patch is the bound on the input rows / columns one 4 x 16 output tile reads, the
+ * bytes its LDS (forward; 0 in the backward; saturated at INT32_MAX).  sy, sx = (in - 1) / (out - 1) in float (0 when
+ * out == 1) and, for the backward, isy, isx = 1 / s (out when s == 0) as int32 bit images.  -1 on a bad argument. */
+int evk_upsample_bilinear_plan(int32_t N, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t C, int32_t vec,
+                               int32_t backward, int32_t* out);
 /* The same resampling with y / dy the channel slice [c0, c0 + C) of a [N,Ho,Wo,Ctot] map (the same kernels, another pixel
  * stride: bit-identical to the dense calls) — hrnet_head.py:17-25 (SimpleFusion: `torch.cat` of the up-sampled branches):
  * every source is written straight into its place in the concat buffer, and its gradient read straight out of the buffer's.
