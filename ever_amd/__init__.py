@@ -20,9 +20,10 @@ from .core.device import auto_device  # noqa: E402
 from .core.logger import info  # noqa: E402
 from .core.to import to_device, to_tensor  # noqa: E402
 from .interface import (Callback, ConfigurableMixin, ERDataLoader, ERDataset, ERModule,  # noqa: E402
-                        LearningRateBase)
+                        LearningRateBase, MultiTransform, Transform)
 from . import api, data, magic, metric, module, opt, trainer  # noqa: E402,F401
 from .core.launcher import Launcher  # noqa: E402
+from .magic.transform.tta import *  # noqa: E402,F401,F403  (tta, TestTimeAugmentation: at the top level, as the reference)
 
 
 def install_as_ever():

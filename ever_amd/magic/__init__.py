@@ -1,1 +1,1 @@
-from . import bigimage  # noqa: F401
+from . import bigimage, transform  # noqa: F401

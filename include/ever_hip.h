@@ -488,6 +488,38 @@ int evk_hr_fuse_fwd(const float* const* terms, const int32_t* shifts, const floa
 int evk_hr_fuse_bwd(const float* dy, const uint32_t* relu_bits, float* dmasked, float* dpooled1, float* dpooled2,
                     float* dpooled3, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 
+/* The eight symmetries of the square on an NHWC map — magic/transform/segm.py (Rotate90k, HorizontalFlip, VerticalFlip,
+ * Transpose) — and their fused mean — magic/transform/tta.py: `sum(outs) / len(outs)` (csrc/d4.hip).
+ * op = swap | flip_rows << 1 | flip_cols << 2 acts on x: [N,Hi,Wi,C] and gives y: [N,Ho,Wo,C], (Ho, Wo) = swap ? (Wi, Hi) :
+ * (Hi, Wi):  y[n,r,c,:] = x[n,a,b,:] with r' = flip_rows ? Ho-1-r : r, c' = flip_cols ? Wo-1-c : c, (a, b) = swap ? (c', r') :
+ * (r', c') — transpose first, then flip.  In NCHW terms: flip(x, [2]) = 2, flip(x, [3]) = 4, transpose(2, 3) = 1,
+ * rot90(x, 1, [2,3]) = 3, rot90(x, 2, [2,3]) = 6, rot90(x, 3, [2,3]) = 5, the anti-transpose = 7.  The inverse of 3 is 5 and
+ * of 5 is 3; every other op is its own inverse.  A dense NCHW map is the same call with N' = N*C, C' = 1.
+ * evk_d4_apply is a pure copy of 32-bit words (NaN payloads, infinities, -0.0 keep their bits); op 0 copies.  x and y may
+ * not overlap.  Index arithmetic is 32-bit: all three entry points return -2 for N*Hi*Wi*C >= 2^31, before any launch;
+ * -1: null pointer, non-positive size, op outside 0..7. */
+int evk_d4_apply(const float* x, float* y, int32_t N, int32_t Hi, int32_t Wi, int32_t C, int32_t op, void* stream);
+/* y[i] = s / (float)count (count > 0; a correctly rounded fp32 division) or s (count == 0), where
+ * s = (acc ? acc[i] : 0.0f) + T_0(t_0)[i], then s += T_k(t_k)[i] for k = 1 .. nterms-1 in that order: bit for bit the
+ * reference's `sum(outs) / len(outs)` (sequential fp32 adds from 0, so an all -0.0 sum is +0.0).  T_k is ops[k] as above and
+ * terms[k] has the dims ops[k] implies for an [N,Ho,Wo,C] result: [N,Wo,Ho,C] for a swap op.  terms and ops are HOST arrays
+ * of nterms entries read during the call, 1 <= nterms <= 16 (-2 otherwise); a longer list is chained through acc
+ * [N,Ho,Wo,C] with count = 0 on all calls but the last, which keeps the order of additions.  y may alias acc, not a term
+ * (-1).  One launch: every term takes the path evk_d4_plan names for its shape, a direct read or the LDS tile. */
+int evk_d4_merge(const float* const* terms, const int32_t* ops, int32_t nterms, const float* acc, float* y, int32_t N,
+                 int32_t Ho, int32_t Wo, int32_t C, int32_t count, void* stream);
+/* Host only, no launch: the kernel a term x: [N,Hi,Wi,C] under `op` takes in evk_d4_apply and evk_d4_merge (both decide
+ * through this function; tests pick their shapes with it).  out[6] = { kernel, tile rows, tile columns, LDS row stride in
+ * floats, LDS bytes, elements per thread }.  kernel: 0 element per thread, scalar; 1 element per thread, 16-byte (C % 4 == 0;
+ * the launchers fall back to 0 for a pointer off the 16-byte grid); 2 LDS tile (swap ops on narrow pixels; the last five
+ * numbers are 0 otherwise).  Return codes as evk_d4_apply. */
+int evk_d4_plan(int32_t N, int32_t Hi, int32_t Wi, int32_t C, int32_t op, int32_t* out);
+/* For measurements and tests only (tools/bench_tta.py, tests/test_d4_gpu.py); the package never calls it.  From now on, in
+ * this process, evk_d4_plan and both launchers name `kernel` (0, 1 or 2 as above) wherever that kernel is legal for the term
+ * (1 needs C % 4 == 0, 2 a swap op and C <= 64) and follow their own rule elsewhere; any other value, -1 by custom, restores
+ * the rule everywhere.  Returns the previous setting (-1: none). */
+int evk_d4_force_kernel(int32_t kernel);
+
 /* F.adaptive_avg_pool2d(x, 1) — fs_relation.py:177. x: [N,HW,C] -> y: [N,C]. */
 int evk_gap_fwd(const float* x, float* y, int32_t N, int32_t HW, int32_t C, void* stream);
 int evk_gap_bwd(const float* dy, float* dx, int32_t N, int32_t HW, int32_t C, void* stream);

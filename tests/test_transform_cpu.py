@@ -1,0 +1,212 @@
+"""Test-time augmentation without a GPU: the public names under both package names, the transforms and `tta` on CPU tensors
+(the reference's torch expressions, against tests/golden/tta_ref.npz bit for bit), and the exported plan of the dihedral kernels
+against the table of GPU cases in tests/tta_common.py."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from tests import tta_common as tc
+
+
+def _lib():
+    from ever_amd import _C
+    return _C.load()
+
+
+def _golden():
+    return {k: torch.from_numpy(v) for k, v in np.load(tc.GOLDEN).items()}
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def test_public_names_under_both_package_names():
+    import ever_amd as er
+    er.install_as_ever()
+    import ever
+    import ever.magic.transform.segm as segm
+    import ever.magic.transform.tta as tta_mod
+    for pkg in (er, ever):
+        assert issubclass(pkg.MultiTransform, list) and pkg.Transform is pkg.interface.Transform
+        assert pkg.interface.MultiTransform is pkg.MultiTransform
+        for name in ('Identity', 'Rotate90k', 'HorizontalFlip', 'VerticalFlip', 'Transpose', 'Scale'):
+            assert issubclass(getattr(pkg.magic.transform.segm, name), pkg.Transform), name
+        assert callable(pkg.magic.transform.tta.tta) and issubclass(pkg.magic.transform.tta.TestTimeAugmentation, torch.nn.Module)
+        assert pkg.tta is pkg.magic.transform.tta.tta and pkg.TestTimeAugmentation is pkg.magic.transform.tta.TestTimeAugmentation
+    assert segm is er.magic.transform.segm and tta_mod is er.magic.transform.tta
+    from ever_amd.hip import functional as HF
+    assert callable(HF.d4) and callable(HF.d4_mean)
+
+
+def test_unit_test_of_every_transform_on_cpu_tensors():
+    """as the `__main__` block of the reference's segm.py runs it"""
+    from ever_amd.interface import Transform
+    from ever_amd.magic.transform import segm
+    for k in (1, 2, 3):
+        Transform.unit_test(segm.Rotate90k(k=k))
+    for t in (segm.Identity(), segm.HorizontalFlip(), segm.VerticalFlip(), segm.Transpose()):
+        Transform.unit_test(t)
+    for scale_factor in np.linspace(0.25, 2.0, num=int((2.0 - 0.25) / 0.25 + 1)):
+        Transform.unit_test(segm.Scale(scale_factor=float(scale_factor)))
+    Transform.unit_test(segm.Scale(scale_factor=float(0.49)))
+    Transform.unit_test(segm.Scale(size=(894, 896)))
+
+
+def test_asserts_are_the_references():
+    import ever_amd as er
+    from ever_amd.magic.transform import segm
+    for k in (0, 4):
+        with pytest.raises(AssertionError):
+            segm.Rotate90k(k)
+    with pytest.raises(AssertionError):
+        er.MultiTransform(segm.Identity(), torch.flip)
+    with pytest.raises(NotImplementedError):
+        er.Transform().transform(torch.zeros(1, 1, 2, 2))
+
+
+def test_transforms_are_the_ops_the_kernels_implement():
+    """every transform class against the op encoding of include/ever_hip.h, on a CPU tensor; inverses undo"""
+    from ever_amd.hip.transform import d4_inverse
+    from ever_amd.magic.transform import segm
+    x = torch.arange(2 * 3 * 5 * 7, dtype=torch.float32).view(2, 3, 5, 7)
+    table = [(segm.Identity(), 0), (segm.Transpose(), tc.TRANSPOSE_OP), (segm.VerticalFlip(), tc.VFLIP_OP),
+             (segm.HorizontalFlip(), tc.HFLIP_OP)] + [(segm.Rotate90k(k), op) for k, op in tc.ROT90_OPS.items()]
+    for t, op in table:
+        assert t.d4_op == op, (type(t).__name__, t.d4_op, op)
+        assert torch.equal(t.transform(x), tc.d4_ref(x, op)), type(t).__name__
+        assert torch.equal(t.inv_transform(t.transform(x)), x), type(t).__name__
+    for op in range(8):
+        assert d4_inverse(op) == tc.INVERSE[op]
+        assert torch.equal(tc.d4_ref(tc.d4_ref(x, op), tc.INVERSE[op]), x), op
+        assert torch.equal(segm.d4_torch(x, op), tc.d4_ref(x, op)), op
+    assert torch.equal(torch.rot90(x, 1, [2, 3]), tc.d4_ref(x, 1 | 2))
+    assert torch.equal(torch.rot90(x, 3, [2, 3]), tc.d4_ref(x, 1 | 4))
+    assert torch.equal(torch.rot90(x, 2, [2, 3]), tc.d4_ref(x, 2 | 4))
+
+
+def test_int64_label_map_round_trip():
+    from ever_amd.magic.transform import segm
+    y = torch.randint(0, 255, (2, 1, 9, 13), dtype=torch.int64)
+    t = segm.Rotate90k(1)
+    z = t.transform(y)
+    assert z.dtype == torch.int64 and z.shape == (2, 1, 13, 9) and torch.equal(z, torch.rot90(y, 1, [2, 3]))
+    assert torch.equal(t.inv_transform(z), y)
+
+
+def test_cpu_tensors_never_reach_the_kernel_wrappers():
+    from ever_amd.hip import functional as HF
+    x = torch.zeros(1, 1, 2, 2)
+    with pytest.raises(HF.HipPathError):
+        HF.d4(x, 1)
+    with pytest.raises(HF.HipPathError):
+        HF.d4_mean([x], [0])
+
+
+@pytest.mark.parametrize('name', tc.FIXTURE_SETS)
+def test_tta_on_cpu_equals_the_reference_bit_for_bit(name):
+    import ever_amd as er
+    from ever_amd.magic.transform import segm
+    from ever_amd.magic.transform.tta import TestTimeAugmentation, tta
+    g = _golden()
+    assert tuple(g['input'].shape) == tc.FIXTURE_SHAPE
+    cfg = tc.fixture_sets(segm, er.Transform)[name]
+    for t, im in zip(cfg, er.MultiTransform(*cfg).transform(g['input'])):
+        want = g['input'] if type(t).__name__ == 'Identity' else g['in_' + tc.transform_label(t)]
+        assert _same_bits(im, want), (name, tc.transform_label(t))
+    assert _same_bits(tta(tc.toy_model, g['input'], cfg), g[name])
+    assert _same_bits(TestTimeAugmentation(tc.toy_model, cfg)(g['input']), g[name])
+
+
+# ------------------------------------------------------------------------------------------------ the plan
+def test_every_apply_case_lands_on_the_kernel_it_names():
+    lib = _lib()
+    for case in tc.APPLY_CASES:
+        n, h, w, c, op, kernel = case
+        got = tc.plan(lib, n, h, w, c, op)
+        assert got[0] == kernel, (case, tc.KERNEL_NAMES[got[0]])
+        if kernel == tc.TILE:
+            tr, tcols, stride, lds, per = got[1:]
+            assert tr == tcols and tr > 0 and tr * c * 4 >= 128, (case, got)       # full cache lines on both sides
+            assert stride >= tr * c and stride % 32 == c % 32, (case, got)          # the conflict-free row stride
+            assert lds == tr * stride * 4 <= 64 * 1024 and per == -(-tr * tr * c // 256) <= 16, (case, got)
+        else:
+            assert got[1:] == (0, 0, 0, 0, 0), (case, got)
+    assert 90 <= len(tc.APPLY_CASES) <= 120
+
+
+def test_every_kernel_is_reached_under_every_swap_op_and_at_its_edges():
+    for kernel in (tc.SCALAR, tc.VEC, tc.TILE):
+        for op in tc.SWAP_OPS:
+            assert any(c[4] == op and c[5] == kernel for c in tc.APPLY_CASES), (tc.KERNEL_NAMES[kernel], op)
+    for kernel in (tc.SCALAR, tc.VEC):
+        for op in tc.PLAIN_OPS:
+            assert any(c[4] == op and c[5] == kernel for c in tc.APPLY_CASES), (tc.KERNEL_NAMES[kernel], op)
+    lib = _lib()
+    # the tile kernel: both tile sizes the cases reach, each with a map one short of / one past a tile edge on either axis,
+    # whole tiles, more than one tile, and maps smaller than a tile
+    tiles = {}
+    for n, h, w, c, op, kernel in tc.APPLY_CASES:
+        if kernel == tc.TILE:
+            tiles.setdefault(tc.plan(lib, n, h, w, c, op)[1], set()).add((h, w))
+    assert len(tiles) >= 2, tiles
+    for t, maps in tiles.items():
+        assert any(h % t == t - 1 and w % t == 1 for h, w in maps), (t, maps)
+        assert any(h % t == 1 and w % t == t - 1 for h, w in maps), (t, maps)
+        assert any(h % t == 0 and w >= t for h, w in maps) and any(h > t or w > t for h, w in maps), (t, maps)
+        assert {(1, 1), (1, 7), (7, 1)} <= maps, (t, maps)
+
+
+def test_forced_cases_reach_their_kernel():
+    lib = _lib()
+    assert lib.evk_d4_force_kernel(-1) == -1                  # nothing in the package sets it
+    for n, h, w, c, op, kernel in tc.FORCED_CASES:
+        unforced = tc.plan(lib, n, h, w, c, op)[0]
+        assert unforced != kernel, (n, h, w, c, op)            # a case the rule reaches belongs in APPLY_CASES
+        with tc.forced(lib, kernel):
+            assert tc.plan(lib, n, h, w, c, op)[0] == kernel, (n, h, w, c, op)
+        assert tc.plan(lib, n, h, w, c, op)[0] == unforced
+    # a forced kernel that is not legal for the shape is ignored
+    with tc.forced(lib, tc.TILE):
+        assert tc.plan(lib, 1, 8, 8, 4, 0)[0] == tc.VEC and tc.plan(lib, 1, 8, 8, 65, 1)[0] == tc.SCALAR
+    with tc.forced(lib, tc.VEC):
+        assert tc.plan(lib, 1, 8, 8, 3, 1)[0] != tc.VEC
+    assert lib.evk_d4_force_kernel(-1) == -1
+
+
+def test_every_merge_case_lands_on_the_kernel_it_names():
+    lib = _lib()
+    for case in tc.MERGE_CASES:
+        n, c, ho, wo, nt, kind, kernel = case
+        ops = tc.merge_ops(nt, kind)
+        for i in range(0, nt, tc.MAX_TERMS):
+            got = tc.merge_kernel(lib, n, c, ho, wo, ops[i:i + tc.MAX_TERMS])
+            if i == 0 or kind == 'plain':
+                assert got == kernel, (case, i, tc.KERNEL_NAMES[got])
+    assert {c[4] for c in tc.MERGE_CASES} >= {1, 2, 3, 7, 8, 16, 17}
+    assert {c[6] for c in tc.MERGE_CASES} == {tc.SCALAR, tc.VEC, tc.TILE}
+
+
+def test_plan_refuses_bad_and_oversized_arguments():
+    lib = _lib()
+    out = (ctypes.c_int32 * 6)()
+    assert lib.evk_d4_plan(1, 4, 4, 4, 0, None) == -1
+    for bad in ((1, 4, 4, 4, -1), (1, 4, 4, 4, 8), (0, 4, 4, 4, 1), (1, 0, 4, 4, 1), (1, 4, -3, 4, 1), (1, 4, 4, 0, 1)):
+        assert lib.evk_d4_plan(*bad, out) == -1, bad
+    # 32-bit indices: 2^31 elements and more are refused before any launch, one fewer is taken
+    assert lib.evk_d4_plan(4, 32768, 16384, 1, 1, out) == -2 and b'2147483648' in lib.evk_last_error()
+    assert lib.evk_d4_plan(2, 65536, 65536, 4, 0, out) == -2
+    assert lib.evk_d4_plan(1, 2 ** 31 - 1, 1, 1, 3, out) == 0
+    # the launchers decide through the same function: they refuse the same arguments without touching a pointer
+    one = ctypes.c_void_p(16)
+    assert lib.evk_d4_apply(one, one, 4, 32768, 16384, 1, 1, None) == -2
+    assert lib.evk_d4_apply(one, one, 1, 4, 4, 4, 8, None) == -1
+    assert lib.evk_d4_apply(None, one, 1, 4, 4, 4, 1, None) == -1
+    terms, ops = (ctypes.c_void_p * 1)(32), (ctypes.c_int32 * 1)(1)
+    assert lib.evk_d4_merge(terms, ops, 1, None, one, 4, 32768, 16384, 1, 1, None) == -2
+    assert lib.evk_d4_merge(terms, ops, 0, None, one, 1, 4, 4, 4, 1, None) == -2
+    assert lib.evk_d4_merge(terms, ops, 17, None, one, 1, 4, 4, 4, 1, None) == -2
+    assert lib.evk_d4_merge(terms, ops, 1, None, ctypes.c_void_p(32), 1, 4, 4, 4, 1, None) == -1      # y aliases a term
+    assert lib.evk_d4_merge(terms, ops, 1, None, one, 1, 4, 4, 4, -1, None) == -1
