@@ -138,6 +138,10 @@ SIGNATURES = {
     'evk_upsample_bilinear_slice_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_hr_fuse_fwd': (c_int, [P, P, P, c_i32, P, P, P, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_hr_fuse_bwd': (c_int, [P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_wfuse_fwd': (c_int, [P, P, c_i32, P, c_i32, c_f32, P, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_wfuse_bwd': (c_int, [P, P, P, c_i32, P, c_i32, c_f32, P, P, P, c_i64, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_wfuse_workspace_bytes': (c_size_t, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    'evk_wfuse_plan': (c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
     'evk_d4_apply': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_d4_merge': (c_int, [P, P, c_i32, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_d4_plan': (c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),

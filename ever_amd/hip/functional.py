@@ -13,6 +13,7 @@ The wrappers live in one module per kernel family (round 6: this file used to ho
   losses.py      BCE / dice / CE / soft-CE / tversky / focal / confusion matrix
   depthwise.py   depthwise convolution (groups == channels), the broadcast of a 1x1 map
   hr.py          HRNet: the multi-resolution exchange as one node, bilinear up-sampling into a concat buffer
+  fuse.py        BiFPN: the learned weighted fusion node, nearest x2 as an index shift
   transform.py   test-time augmentation: the eight symmetries of the square as one copy, their fused mean
 and every name of theirs is visible here, so `from ever_amd.hip import functional as HF; HF.conv2d(...)` and the
 `HF._X` switches that tests and tools read and set keep working: reading goes through this module's own dictionary (filled
@@ -24,16 +25,16 @@ Reference call sites replaced (ever/module/...): see the per-function docstrings
 import sys
 import types
 
-from . import _base, streams, conv, norm, pointwise, losses, depthwise, hr, transform
+from . import _base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform
 
 __all__ = [
     'HipPathError', 'empty_nhwc', 'as_nhwc', 'is_nhwc', 'image_to_nhwc', 'conv2d', 'conv2d_fork', 'conv_transpose2d', 'batch_norm_act', 'relu',
     'max_pool3x3s2', 'upsample_nearest2x_add', 'upsample_bilinear', 'global_avg_pool', 'fs_relation',
     'mean4', 'add', 'bce_with_logits', 'dice_loss_with_logits', 'cross_entropy', 'soft_cross_entropy',
-    'depthwise_conv2d', 'broadcast_hw', 'hr_fuse', 'bilinear_concat', 'd4', 'd4_mean',
+    'depthwise_conv2d', 'broadcast_hw', 'hr_fuse', 'bilinear_concat', 'd4', 'd4_mean', 'weighted_fuse', 'upsample_nearest2x',
 ]
 
-_PARTS = (_base, streams, conv, norm, pointwise, losses, depthwise, hr, transform)
+_PARTS = (_base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform)
 for _m in _PARTS:            # later families win: conv.conv2d (the traceable wrapper) over nothing, pointwise.relu over _base's none
     for _k, _v in vars(_m).items():
         if not (_k.startswith('__') and _k.endswith('__')):

@@ -4,7 +4,7 @@ from .changestar import ChangeMixin, ChangeStarFarSeg
 from .deeplab import DeepLabV3Plus
 from .deeplabv3p_head import Deeplabv3pDecoder, Deeplabv3pHead
 from .farseg import FarSeg, FarSegPP
-from .fpn import FPN, AssymetricDecoder
+from .fpn import FPN, AssymetricDecoder, BiFPN, FastNormalizedFusionConv3x3, Fusion, NormalizedFusionConv3x3
 from .freenet import FreeNet
 from .hrnet import HRNetEncoder
 from .hrnet_head import HRNetHead, SimpleFusion
@@ -21,4 +21,5 @@ __all__ = ['ResNetEncoder', 'FPN', 'AssymetricDecoder', 'FSRelation', 'FSRelatio
            'AdaptiveAvgPool2d', 'HipSequential', 'to_hip', 'loss',
            'DepthwiseConv2d', 'SeparableConv2d', 'SeparableConvBlock', 'PoolBlock', 'AtrousSpatialPyramidPool', 'ASPPHead',
            'Deeplabv3pDecoder', 'Deeplabv3pHead', 'DeepLabV3Plus',
-           'HighResolutionModule', 'HighResolutionNet', 'HRNetEncoder', 'SimpleFusion', 'HRNetHead', 'HRNetSeg']
+           'HighResolutionModule', 'HighResolutionNet', 'HRNetEncoder', 'SimpleFusion', 'HRNetHead', 'HRNetSeg',
+           'Fusion', 'FastNormalizedFusionConv3x3', 'NormalizedFusionConv3x3', 'BiFPN']

@@ -1,22 +1,29 @@
-"""FPN and the asymmetric decoder of FarSeg (API of reference ever/module/fpn.py:40-115,144-193).
+"""FPN, the asymmetric decoder of FarSeg and BiFPN (API of reference ever/module/fpn.py:40-115,144-193,196-309).
 
 FPN convs carry NO bias / BN / ReLU (kaiming_uniform a=1); the top-down path is nearest x2 fused with
 the lateral add; decoder branches are [conv3x3 -> BN -> ReLU -> bilinear x2(align_corners)] x n, the
 four branches are averaged, the classifier conv has a bias and is followed by bilinear x scale.
 Module names / Sequential indices equal the reference's, so state-dict keys are identical
 (`fpn_inner1.0.weight`, `blocks.3.2.0.weight`, `classifier.0.bias`, ...).
+
+BiFPN: every node `sum_k w^_k x_k` (Fusion) is one pass of the fusion kernel (HF.weighted_fuse) with the learned weights
+normalised on the device, and the top-down path's UpsamplingNearest2d enters it as an index shift: no up-sampled tensor, no
+stack, no product tensor.  Keys as the reference's (`bin_fusion_modules.0.0.weights`, `...0.1.0.weight`, `...0.2.running_mean`).
 """
 import math
 import os
 
+import torch
 import torch.nn as nn
 
 from ..hip import functional as HF
-from .layers import BatchNorm2d, Conv2d, Dropout, GELU, GroupNorm, HipSequential, ReLU, UpsamplingBilinear2d
-from .ops import Bf16compatible, ConvBlock
+from .layers import (BatchNorm2d, Conv2d, Dropout, GELU, GroupNorm, HipSequential, MaxPool2d, ReLU, UpsamplingBilinear2d,
+                     UpsamplingNearest2d, run_sequence)
+from .ops import Bf16compatible, ConvBlock, SeparableConv2d
 
 __all__ = ['FPN', 'AssymetricDecoder', 'LastLevelMaxPool', 'LastLevelP6P7', 'conv_with_kaiming_uniform',
-           'default_conv_block', 'conv_bn_block', 'conv_bn_relu_block']
+           'default_conv_block', 'conv_bn_block', 'conv_bn_relu_block',
+           'Fusion', 'FastNormalizedFusionConv3x3', 'NormalizedFusionConv3x3', 'BiFPN']
 
 
 def init_conv(m):
@@ -278,6 +285,126 @@ class AssymetricDecoder(nn.Module):
                 out = HF.add(out, t)
             out = _Scale.apply(out, 1.0 / len(zs))
         return run_sequence(list(self.classifier)[1:], out)
+
+
+class Fusion(nn.Module):
+    """reference fpn.py:196-224: `sum_k w^_k x_k` over a list of equally shaped maps, w^ = fast_normalize(weights) =
+    relu(w) / (sum relu(w) + eps) or softmax(weights): one pass of the fusion kernel, which normalises the raw parameter
+    itself (HF.weighted_fuse; 2 to 4 inputs)."""
+    eps = 0.0001
+
+    def __init__(self, num_inputs, norm_method='fast_normalize'):
+        super().__init__()
+        assert num_inputs > 1
+        self.norm_method = norm_method
+        self.weights = nn.Parameter(torch.Tensor(num_inputs))
+        assert norm_method in ['softmax', 'fast_normalize']
+        self.reset_parameters()
+
+    def forward(self, features):
+        return HF.weighted_fuse([(f, 0) for f in features], self.weights, self.norm_method, Fusion.eps)
+
+    def reset_parameters(self):
+        if self.norm_method == 'softmax':
+            nn.init.zeros_(self.weights)
+        elif self.norm_method == 'fast_normalize':
+            nn.init.ones_(self.weights)
+
+
+def _hooked(*mods):
+    return any(m._forward_hooks or m._forward_pre_hooks for m in mods)
+
+
+class _FusionConv3x3(HipSequential):
+    """Fusion -> SeparableConv2d 3x3 -> BatchNorm2d -> ReLU (reference fpn.py:227-244), children '0' .. '3'."""
+
+    def __init__(self, num_inputs, in_channels, out_channels, norm_method):
+        super().__init__(
+            Fusion(num_inputs, norm_method),
+            SeparableConv2d(in_channels, out_channels, 3, 1, 1),
+            BatchNorm2d(out_channels),
+            ReLU(True),
+        )
+
+    def forward(self, features, shifts=None):
+        """shifts (BiFPN only): features[k] is `[N, C, H >> shifts[k], W >> shifts[k]]` and enters the node as an index shift
+        instead of through an up-sampling module"""
+        fusion = self[0]
+        if shifts is None:
+            x = fusion(features)
+        else:
+            x = HF.weighted_fuse(list(zip(features, shifts)), fusion.weights, fusion.norm_method, Fusion.eps)
+        # one sequence, so that the pointwise convolution sees the BatchNorm after it (statistics from its epilogue)
+        sep = self[1]
+        mods = (list(sep) if type(sep) is SeparableConv2d and not _hooked(sep) else [sep]) + list(self)[2:]
+        return run_sequence(mods, x)
+
+
+class FastNormalizedFusionConv3x3(_FusionConv3x3):
+    def __init__(self, num_inputs, in_channels, out_channels):
+        super().__init__(num_inputs, in_channels, out_channels, 'fast_normalize')
+
+
+class NormalizedFusionConv3x3(_FusionConv3x3):
+    def __init__(self, num_inputs, in_channels, out_channels):
+        super().__init__(num_inputs, in_channels, out_channels, 'softmax')
+
+
+class BiFPN(nn.Module):
+    """reference fpn.py:247-309: a top-down pass of two-input nodes, then a bottom-up pass of three-input nodes, over maps at
+    `feature_strides`; where a stride repeats (e.g. [4, 8, 16, 16]) a 1x1 Conv-BN-ReLU takes the place of the resampling.
+    forward consumes the list it is given (`pop()`, as the reference) and returns the maps finest first."""
+
+    def __init__(self, in_channels, feature_strides, normalized_fusion='fast_normalize', downsample_op='conv'):
+        super().__init__()
+        cs = max(feature_strides)
+        nf_op = FastNormalizedFusionConv3x3 if normalized_fusion == 'fast_normalize' else NormalizedFusionConv3x3
+        self.feature_strides = feature_strides
+
+        def conv1x1_bn_relu():
+            return HipSequential(Conv2d(in_channels, in_channels, 1), BatchNorm2d(in_channels), ReLU(True))
+        self.bin_fusion_modules = nn.ModuleList([nf_op(2, in_channels, in_channels) for _ in range(len(feature_strides) - 1)])
+        self.triple_fusion_modules = nn.ModuleList([nf_op(3, in_channels, in_channels) for _ in range(len(feature_strides) - 1)])
+        self.upsample_modules = nn.ModuleList([
+            UpsamplingNearest2d(scale_factor=2.) if cs / fs > 1 else conv1x1_bn_relu() for fs in feature_strides[::-1][1:]])
+        self.downsample_modules = nn.ModuleList([
+            HipSequential(Conv2d(in_channels, in_channels, 3, 2, 1) if downsample_op == 'conv' else MaxPool2d(3, 2, 1),
+                          BatchNorm2d(in_channels), ReLU(True))
+            if cs / fs > 1 else conv1x1_bn_relu() for fs in feature_strides[:-1]])
+
+    @staticmethod
+    def _as_index_shift(up, block):
+        """the up-sampling module's input can enter the node shifted: nothing would see the tensor that is not made"""
+        return (type(up) is UpsamplingNearest2d and up.size is None and up.scale_factor == 2
+                and isinstance(block, _FusionConv3x3) and type(block[0]) is Fusion and not _hooked(up, block, block[0])
+                and not HF.observers_active())
+
+    def forward(self, features):
+        # top-down
+        in_features = features.copy()
+        inner_features = []
+        for idx in range(len(self.feature_strides) - 1):
+            x_top = features.pop()
+            x_down = features.pop()
+            up, block = self.upsample_modules[idx], self.bin_fusion_modules[idx]
+            if self._as_index_shift(up, block):
+                inner_feature = block([x_down, x_top], shifts=(0, 1))
+            else:
+                inner_feature = block([x_down, up(x_top)])
+            features.append(inner_feature)
+            inner_features.append(inner_feature)
+
+        inner_features.reverse()
+        inner_features.append(in_features[-1])
+        # bottom-up
+        out_features = [inner_features[0]]
+        for idx in range(len(self.feature_strides) - 1):
+            x_bottom = inner_features.pop(0)
+            x_up = inner_features.pop(0)
+            out_feature = self.triple_fusion_modules[idx]([in_features[idx + 1], x_up, self.downsample_modules[idx](x_bottom)])
+            inner_features.insert(0, out_feature)
+            out_features.append(out_feature)
+        return out_features
 
 
 class _Scale:

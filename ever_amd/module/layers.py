@@ -12,8 +12,8 @@ import torch.nn as nn
 
 from ..hip import functional as HF
 
-__all__ = ['Conv2d', 'ConvTranspose2d', 'BatchNorm2d', 'ReLU', 'MaxPool2d', 'UpsamplingBilinear2d', 'AdaptiveAvgPool2d', 'Identity',
-           'Dropout', 'GELU', 'HipSequential', 'run_sequence', 'to_hip']
+__all__ = ['Conv2d', 'ConvTranspose2d', 'BatchNorm2d', 'ReLU', 'MaxPool2d', 'UpsamplingBilinear2d', 'UpsamplingNearest2d', 'AdaptiveAvgPool2d',
+           'Identity', 'Dropout', 'GELU', 'HipSequential', 'run_sequence', 'to_hip']
 
 Identity = nn.Identity
 
@@ -151,6 +151,18 @@ class UpsamplingBilinear2d(nn.UpsamplingBilinear2d):
         if self.scale_factor is None:
             raise NotImplementedError('ever_amd UpsamplingBilinear2d: give scale_factor')
         return HF.upsample_bilinear(x, self.scale_factor)
+
+
+class UpsamplingNearest2d(nn.UpsamplingNearest2d):
+    """nearest, scale factor 2 only (reference fpn.py:265, BiFPN's top-down path): the one-term, unit-weight call of the
+    fusion kernel.  BiFPN itself hands this module's INPUT to the fusion node as an index-shifted term and runs the module
+    only when a hook wants to see its output."""
+
+    def forward(self, x):
+        if self.size is not None or _one(self.scale_factor) != 2:
+            raise NotImplementedError(f'ever_amd UpsamplingNearest2d: only scale_factor=2 is implemented, got '
+                                      f'size={self.size}, scale_factor={self.scale_factor}')
+        return HF.upsample_nearest2x(x)
 
 
 class AdaptiveAvgPool2d(nn.AdaptiveAvgPool2d):

@@ -488,6 +488,39 @@ int evk_hr_fuse_fwd(const float* const* terms, const int32_t* shifts, const floa
 int evk_hr_fuse_bwd(const float* dy, const uint32_t* relu_bits, float* dmasked, float* dpooled1, float* dpooled2,
                     float* dpooled3, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 
+/* The learned weighted fusion node of a BiFPN — fpn.py:196-224 (Fusion) with the UpsamplingNearest2d of fpn.py:264-269 as an
+ * index shift (csrc/wfuse.hip):  y = ((w^0 t0 + w^1 t1) + w^2 t2) + w^3 t3 over 1 to 4 terms, NHWC fp32.  Term k is
+ * terms[k] = [N, H >> s, W >> s, C] with s = shifts[k] in {0, 1}, read at output pixel (y, x) as its pixel (y >> s, x >> s).
+ * terms and shifts are HOST arrays of nterms entries read during the call.  weights: the RAW [nterms] parameter ON THE
+ * DEVICE, normalised inside the kernel: norm 0 = fast_normalize, r = max(w, 0), w^ = r / (sum r + eps); norm 1 = softmax
+ * (max-subtracted; eps unused); weights == NULL = unit weights (one term with shift 1: plain nearest x2).  Every product
+ * and sum is rounded on its own, and a term whose w^ is 0 is still read and multiplied (its infinities and NaNs propagate).
+ * -1: null pointer or non-positive size.  -2 (with a text): C % 4 != 0, nterms outside 1..4, a shift outside {0, 1}, norm
+ * outside {0, 1}, H or W odd with a shifted term, 2^31 or more 16-byte elements.  All before any launch. */
+int evk_wfuse_fwd(const float* const* terms, const int32_t* shifts, int32_t nterms, const float* weights, int32_t norm,
+                  float eps, float* y, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
+/* Its backward: one read of dy [N,H,W,C], and of each term only when dweights != NULL (terms may be NULL otherwise).
+ * dterms: HOST array of nterms device pointers, each may be NULL: shift 0 gives w^_k dy, shift 1 the sum over each 2 x 2 block
+ * of w^_k dy, (p00 + p01) + (p10 + p11) by the block's one owner.  dweights [nterms] (may be NULL; needs weights): the
+ * gradient with respect to the RAW weights: the dots d_k = sum dy up(t_k) over the whole map, then the Jacobian,
+ * fast_normalize: [w_j > 0] (d_j - sum_k w^_k d_k) / (sum r + eps);  softmax: w^_j (d_j - sum_k w^_k d_k).  The dots use no
+ * atomics: fp32 partials per thread over at most D products, a wave / LDS tree to one record per workgroup in the
+ * workspace, a one-workgroup launch that adds the records in double in a fixed order: the same bits every run.
+ * workspace (16-byte aligned, evk_wfuse_workspace_bytes; needed with dweights only) holds afterwards the records
+ * [grid][4] fp32 and behind them the four dots, rounded to fp32 (float offset out[6] of evk_wfuse_plan).
+ * Error codes as the forward; no output at all is -1, a workspace that is too small -2. */
+int evk_wfuse_bwd(const float* dy, const float* const* terms, const int32_t* shifts, int32_t nterms, const float* weights,
+                  int32_t norm, float eps, float* const* dterms, float* dweights, void* workspace, int64_t workspace_bytes,
+                  int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
+/* 0 for arguments evk_wfuse_plan refuses */
+size_t evk_wfuse_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t nterms);
+/* Host only, no launch: the geometry of evk_wfuse_bwd (tests take their error bound and grid-edge shapes from it).
+ * out[8] = { grid (workgroups = records), threads per workgroup, D (products one thread adds serially into one fp32 partial),
+ * workspace bytes, 1 if a thread owns a 2 x 2 quad (H and W even) else 0 (one 16-byte element), items (quads or elements)
+ * per thread — a workgroup's share is threads x that many consecutive items —, float offset of the dots in the workspace, 0 }.
+ * The grid has no cap: it grows with the map.  Return codes as evk_wfuse_fwd. */
+int evk_wfuse_plan(int32_t N, int32_t H, int32_t W, int32_t C, int32_t nterms, int32_t* out);
+
 /* The eight symmetries of the square on an NHWC map — magic/transform/segm.py (Rotate90k, HorizontalFlip, VerticalFlip,
  * Transpose) — and their fused mean — magic/transform/tta.py: `sum(outs) / len(outs)` (csrc/d4.hip).
  * op = swap | flip_rows << 1 | flip_cols << 2 acts on x: [N,Hi,Wi,C] and gives y: [N,Ho,Wo,C], (Ho, Wo) = swap ? (Wi, Hi) :
