@@ -177,6 +177,7 @@ SIGNATURES = {
     'evk_confusion_matrix': (c_int, [P, P, c_i64, c_i32, P, P]),
     'evk_confusion_from_logits': (c_int, [P, P, c_i64, c_i32, c_i32, P, P]),
     'evk_gn_workspace_bytes': (c_size_t, [c_i32, c_i64, c_i32, c_i32]),
+    'evk_gn_plan': (c_int, [c_i64, c_i32, C.POINTER(c_i32)]),
     'evk_gn_fwd': (c_int, [P, P, P, c_f32, P, P, P, c_i32, c_i64, c_i32, c_i32, c_u32, P, c_size_t, P]),
     'evk_gn_bwd': (c_int, [P, P, P, P, P, P, P, P, P, c_i32, c_i64, c_i32, c_i32, c_u32, P, c_size_t, P]),
     'evk_concat_channels': (c_int, [P, P, P, c_i64, c_i32, c_i32, P]),

@@ -50,12 +50,15 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
   const float* xn = x + (size_t)n * HW * C;
   const float* dn = MODE ? dy + (size_t)n * HW * C : nullptr;
   const float* yn = (MODE && relu) ? y + (size_t)n * HW * C : nullptr;
-  for (int cb = tc; cb < c4; cb += tpc) {
+  // every thread takes every trip (the body holds __syncthreads); past C > 1024 the last trip has columns for some only
+  for (int cb0 = 0; cb0 < c4; cb0 += tpc) {
+    const int cb = cb0 + tc;
+    const bool on = cb < c4;
     f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
     f32x4 pv = {0.f, 0.f, 0.f, 0.f}, mu = pv, is = pv;
-    if (MODE == 0) {
+    if (on && MODE == 0) {
       pv = *reinterpret_cast<const f32x4*>(xn + cb * 4);
-    } else {
+    } else if (on) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int g = (cb * 4 + e) / cg;
@@ -63,7 +66,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
         is[e] = rstd[n * G + g];
       }
     }
-    if (tr < rl)
+    if (on && tr < rl)
       for (int64_t r = r0 + tr; r < r1; r += rl) {
         const size_t o = (size_t)r * C + cb * 4;
         const f32x4 xv = *reinterpret_cast<const f32x4*>(xn + o);
@@ -84,10 +87,27 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
     red[0][threadIdx.x] = s;
     red[1][threadIdx.x] = q;
     __syncthreads();
-    if (tr == 0) {
+    if (on && tr == 0) {
+      // fold the rows in flight in fp64 and round once: with a pivot far from the mean the rl partial sums are large, and
+      // adding up to 256 of them one after the other in fp32 cost the mean more than everything before it
+      double sd[4], qd[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        sd[e] = (double)s[e];
+        qd[e] = (double)q[e];
+      }
       for (int k = 1; k < rl; ++k) {
-        s += red[0][k * tpc + tc];
-        q += red[1][k * tpc + tc];
+        const f32x4 sk = red[0][k * tpc + tc], qk = red[1][k * tpc + tc];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          sd[e] += (double)sk[e];
+          qd[e] += (double)qk[e];
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s[e] = (float)sd[e];
+        q[e] = (float)qd[e];
       }
       float* o = partial + ((size_t)n * nchunk + blockIdx.x) * 2 * C;
       *reinterpret_cast<f32x4*>(o + cb * 4) = s;
@@ -275,6 +295,22 @@ static int gn_check(const char* what, int32_t N, int64_t HW, int32_t C, int32_t 
   EVK_REQUIRE(N > 0 && HW > 0 && C > 0 && G > 0, EVK_E_INVALID, "%s: non-positive dimension", what);
   EVK_REQUIRE(C % 4 == 0 && C % G == 0, EVK_E_UNSUPPORTED, "%s: C=%d must be a multiple of 4 and of G=%d", what, C, G);
   EVK_REQUIRE(N <= 65535, EVK_E_UNSUPPORTED, "%s: batch %d > 65535", what, N);
+  return EVK_OK;
+}
+
+// Host only (no launch): the plan evk_gn_fwd / evk_gn_bwd take for one sample's [HW][C] map.
+// out = {nchunk, rows_per_chunk, tpc, rl}
+extern "C" int evk_gn_plan(int64_t HW, int32_t C, int32_t* out) {
+  EVK_REQUIRE(out, EVK_E_INVALID, "gn_plan: null pointer");
+  int rc = gn_check("gn_plan", 1, HW, C, 1);
+  if (rc) return rc;
+  const GnPlan pl = gn_plan(HW, C);
+  EVK_REQUIRE(pl.rows_per_chunk <= 0x7fffffffLL, EVK_E_UNSUPPORTED, "gn_plan: HW=%lld: rows per chunk exceed int32",
+              (long long)HW);
+  out[0] = pl.nchunk;
+  out[1] = (int32_t)pl.rows_per_chunk;
+  out[2] = pl.tpc;
+  out[3] = pl.rl;
   return EVK_OK;
 }
 

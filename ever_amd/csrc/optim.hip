@@ -26,7 +26,8 @@ __global__ __launch_bounds__(256) void sqnorm_multi_kernel(const float* const* _
   __syncthreads();
   if (threadIdx.x == 0) partial[(size_t)t * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-// total_norm = sqrt(sum partial); coef = min(1, max_norm / (total_norm + 1e-6))   (torch semantics)
+// total_norm = sqrt(sum partial); coef = clamp(max_norm / (total_norm + 1e-6), max = 1)   (torch semantics: a NaN norm
+// gives a NaN coefficient, so one NaN gradient poisons the whole step visibly, as clip_grad_norm_ does)
 __global__ void clip_coef_kernel(const double* __restrict__ partial, int n, float max_norm, float* total_norm,
                                  float* coef) {
   __shared__ double red[4];
@@ -39,7 +40,7 @@ __global__ void clip_coef_kernel(const double* __restrict__ partial, int n, floa
     const float tn = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
     *total_norm = tn;
     const float c = max_norm / (tn + 1e-6f);
-    *coef = c < 1.f ? c : 1.f;
+    *coef = c >= 1.f ? 1.f : c;   // (not c < 1 ? c : 1, not fminf: both turn a NaN quotient into 1)
   }
 }
 

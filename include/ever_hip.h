@@ -686,6 +686,11 @@ int evk_confusion_from_logits(const float* logits, const int64_t* y_true, int64_
 /* nn.GroupNorm(G, C) (+ReLU) on [N, HW, C] — reference fs_relation.py:88-116 (FSRelationV2 scene encoders).
  * flags bit 0: ReLU fused (backward then needs y).  save_mean / save_rstd: [N*G].  C % 4 == 0, C % G == 0. */
 size_t evk_gn_workspace_bytes(int32_t N, int64_t HW, int32_t C, int32_t G);
+/* Host only, no launch: the reduce plan evk_gn_fwd / evk_gn_bwd take for one sample's [HW][C] map (refuses what they
+ * refuse).  out[4] = { row chunks (workgroups per sample), rows per chunk, threads per row (each walks C / 4 / tpc
+ * 16-byte columns), rows in flight per workgroup }.  The workspace holds [N][chunks][2][C] partial sums and 2 N G
+ * coefficients, as floats. */
+int evk_gn_plan(int64_t HW, int32_t C, int32_t* out);
 int evk_gn_fwd(const float* x, const float* gamma, const float* beta, float eps, float* y,
                float* save_mean, float* save_rstd, int32_t N, int64_t HW, int32_t C, int32_t G,
                uint32_t flags, void* workspace, size_t workspace_bytes, void* stream);
