@@ -9,9 +9,9 @@
 //    vector-memory instruction at all; four loader waves issue the ring (their streaming rate scales with the number of
 //    issuing waves: 2 -> 3.0 TB/s, 4 -> 5.8, dma_patterns.hip) and absorb the back-pressure; four store waves, which never
 //    load, write the output (gfx950 counts loads and stores in one in-order vmcnt per wave: the roles must not mix).
-//  * A K step with no exposed LDS latency: the fragment registers are double-buffered across the barrier,
-//        read k-half 1 | MFMAs k-half 0 | barrier (stage g+1 has landed) | read k-half 0 of stage g+1 | MFMAs k-half 1
-//    (conv1x1_sp.hip has the ISA argument), and nothing in the loop tests a run-time switch.
+//  * A K step with no exposed LDS latency: the fragment registers are double-buffered across the barrier (c1_tile.hpp:
+//    c1_step; conv1x1_sp.hip has the ISA argument), and nothing in the loop tests a run-time switch.
+// The ring's LDS image, its source offsets and the fragment reads are c1_tile.hpp's, shared with the other two forms.
 // Sixteen waves, one workgroup per CU, <= 128 registers per lane; LDS = ring of three 32 KB stages + 64 KB staging image.
 // One s_barrier per K step shared by all roles (gfx950 has no named barriers).  Barrier sequence of a workgroup with T tiles
 // of nk steps (G = T nk global steps): P0, B(0) .. B(G-1), E1.
@@ -23,8 +23,7 @@
 // Compile-time ablations (tools/build_variant.sh -DEVK_PS2_ABL=bits): 1 no loader DMA, 4 no compute, 8 no global stores,
 // 16 store waves idle, 32 no staging writes.
 #include "conv_route.hpp"
-#include "x3_common.hpp"
-#include "lds_dma.hpp"
+#include "c1_tile.hpp"
 #include <stdlib.h>
 #include <string.h>
 
@@ -36,9 +35,8 @@ namespace evk {
 
 namespace {
 
-constexpr int kP2Row = BK3 * 4;      // bytes of one activation row of a K step (32 four-byte words)
-constexpr int kP2BM = 128, kP2BN = 128, kP2NST = 3;
-constexpr int kP2AStage = kP2BM * kP2Row, kP2BPlane = kP2BN * kRowBytes, kP2Stage = kP2AStage + 2 * kP2BPlane;
+constexpr int kP2BM = kC1BM, kP2BN = 128, kP2NST = 3;
+constexpr int kP2AStage = C1Stage<kP2BN>::a_bytes, kP2Stage = C1Stage<kP2BN>::bytes;
 constexpr int kP2Ring = kP2NST * kP2Stage;
 constexpr int kP2OutRow = kP2BN * 4;                 // bytes of one staged output row
 constexpr int kP2Staging = kP2BM * kP2OutRow;        // 64 KB
@@ -47,34 +45,16 @@ constexpr int kP2CW = 8, kP2LW = 4, kP2SW = 4;       // compute / loader / store
 constexpr int kP2Waves = kP2CW + kP2LW + kP2SW;
 constexpr int kP2Instr = 16;                         // store instructions (4 rows x 256 B) per store wave and tile
 
-__device__ __forceinline__ void p2_dma16s(i32x4 rsrc, uint32_t lds_byte, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds"
-               :: "v"(voff), "s"(lds_byte), "s"(rsrc), "s"(soff) : "memory", "m0");
-}
 // the activation stream with the non-temporal hint: a row tile is read by tiles_n workgroups of one XCD — with one or two
 // column tiles the hint is ahead (same box, us: 256 -> 256 @128^2 197 -> 187, 64 -> 256 92 -> 87, 256 -> 128 94 -> 90), with
-// four it evicts what the neighbours are about to read (128 -> 512 @64^2 51 -> 58): the launcher decides (template NT)
-template <bool NT>
-__device__ __forceinline__ void p2_dma16s_a(i32x4 rsrc, uint32_t lds_byte, uint32_t voff, uint32_t soff) {
-  if constexpr (NT) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen nt lds"
-                 :: "v"(voff), "s"(lds_byte), "s"(rsrc), "s"(soff) : "memory", "m0");
-  } else {
-    p2_dma16s(rsrc, lds_byte, voff, soff);
-  }
-}
+// four it evicts what the neighbours are about to read (128 -> 512 @64^2 51 -> 58): the launcher decides (template NT of the
+// kernel -> dma16s_loader<NT>)
+
 // (ablation bit 64: no barrier at all — the loop's own speed; results are garbage)
 __device__ __forceinline__ void p2_barrier() {
   if (EVK_PS2_ABL & 64) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   else ring_barrier();
 }
-__device__ __forceinline__ u32x4 p2_lds_read16(uint32_t lds_byte) {
-  return *(const __attribute__((address_space(3))) u32x4*)(uintptr_t)lds_byte;
-}
-__device__ __forceinline__ void p2_lds_write16(uint32_t lds_byte, f32x4 v) {
-  *(__attribute__((address_space(3))) f32x4*)(uintptr_t)lds_byte = v;
-}
-__device__ __forceinline__ int p2_arow_off(int row, int c) { return row * kP2Row + ((c ^ ((row >> 1) & 7)) << 4); }
 // staged output: 16-byte chunk c (0..31) of row `row` (conv1x1_ps.hip: ps_out_off)
 __device__ __forceinline__ uint32_t p2_out_off(int row, int c) { return (uint32_t)(row * kP2OutRow + ((c ^ (row & 7)) << 4)); }
 
@@ -83,9 +63,7 @@ __device__ __forceinline__ uint32_t p2_out_off(int row, int c) { return (uint32_
 template <bool PK, bool STATS, bool NT>
 __global__ __launch_bounds__(64 * kP2Waves) void conv1x1_ps2_kernel(const IGemmArgs p, uint32_t src_bytes, uint32_t wgt_bytes) {
   constexpr int BM = kP2BM, BN = kP2BN, WM = 32, WN = 64, NB = 2, NST = kP2NST;
-  constexpr int AI = kP2AStage / 1024 / kP2LW;        // activation DMA instructions per loader wave and stage (8 rows each)
-  constexpr int BI = 2 * kP2BPlane / 1024 / kP2LW;    // weight-plane DMA instructions per loader wave and stage
-  constexpr int PER = AI + BI;
+  constexpr int AI = C1Stage<BN>::a_instr(kP2LW), BI = C1Stage<BN>::b_instr(kP2LW), PER = AI + BI;   // per loader wave and stage
   static_assert(AI == 4 && BI == 4 && NST == 3, "tile shape");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_p2[];
@@ -108,49 +86,20 @@ __global__ __launch_bounds__(64 * kP2Waves) void conv1x1_ps2_kernel(const IGemmA
     // ================================================================== loader waves
     const int lw = wave - kP2CW;
     const i32x4 rs_a = make_rsrc(p.src, src_bytes), rs_b = make_rsrc(p.wgt3, wgt_bytes);
-    const uint32_t plane_bytes = (uint32_t)p.Cd * (uint32_t)p.Kpad * 2u;
     uint32_t a_voff[AI], b_voff[BI];
-#pragma unroll
-    for (int t = 0; t < BI; ++t) {     // weights: the same column tile for every row tile of this workgroup
-      const int s = 64 * (BI * lw + t) + lane;
-      const int pt = s / (BN * 4);
-      const int row = (s - pt * BN * 4) >> 2;
-      const int c = (s & 3) ^ ((row >> 2) & 3);
-      const int co = n0 + row;
-      b_voff[t] = co < p.Cd ? (uint32_t)pt * plane_bytes + (uint32_t)co * (uint32_t)p.Kpad * 2u + (uint32_t)c * 16u : kDmaOOB;
-    }
-    auto tile_offsets = [&](int item) {
-      const int m0 = item * BM;
-#pragma unroll
-      for (int t = 0; t < AI; ++t) {
-        const int row = 8 * (AI * lw + t) + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        const int m = m0 + row;
-        uint32_t off = kDmaOOB;
-        if (m < p.M) {
-          const int hw = p.Hm * p.Wm;
-          const int n = m / hw;
-          const int rem = m - n * hw;
-          const int gy = rem / p.Wm;
-          const int gx = rem - gy * p.Wm;
-          const int sy = gy * p.ash + p.oy0, sx = gx * p.asw + p.ox0;
-          if ((unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws)
-            off = (uint32_t)(((n * p.Hs + sy) * p.Ws + sx) * p.Cs) * 4u + (uint32_t)c * 16u;
-        }
-        a_voff[t] = off;
-      }
-    };
+    c1_b_voff<BN, BI>(p, n0, lw, lane, b_voff);   // weights: the same column tile for every row tile of this workgroup
+    auto tile_offsets = [&](int item) { c1_a_voff<AI>(p, item * BM, lw, lane, a_voff); };
     // the issue cursor: (tile i_j, step i_kt) = global stage i_g, into slot S_i
     int i_j = 0, i_kt = 0;
     uint32_t S_i = lds0;
     tile_offsets(grp);
     auto issue_next = [&]() {
       if (!(EVK_PS2_ABL & 1)) {
-        const uint32_t ka = (uint32_t)i_kt * kP2Row, kb = (uint32_t)i_kt * kRowBytes;
+        const uint32_t ka = c1_a_soff(i_kt), kb = c1_b_soff(i_kt);
 #pragma unroll
-        for (int t = 0; t < AI; ++t) p2_dma16s_a<NT>(rs_a, S_i + (AI * lw + t) * 1024, a_voff[t], ka);
+        for (int t = 0; t < AI; ++t) dma16s_loader<NT>(rs_a, S_i + (AI * lw + t) * 1024, a_voff[t], ka);
 #pragma unroll
-        for (int t = 0; t < BI; ++t) p2_dma16s(rs_b, S_i + kP2AStage + (BI * lw + t) * 1024, b_voff[t], kb);
+        for (int t = 0; t < BI; ++t) dma16s_loader(rs_b, S_i + kP2AStage + (BI * lw + t) * 1024, b_voff[t], kb);
       }
       S_i = S_i == lds0 + (NST - 1) * kP2Stage ? lds0 : S_i + kP2Stage;
       if (++i_kt == nk) {
@@ -176,85 +125,46 @@ __global__ __launch_bounds__(64 * kP2Waves) void conv1x1_ps2_kernel(const IGemmA
     // ================================================================ compute waves
     const int li = lane & 31, lh = lane >> 5;
     const int wm = wave & 3, wn = wave >> 2;
-    uint32_t fa_off[2][2], fb_off[2];   // fragment read offsets inside a stage (lane constants)
-    {
-      const int row = wm * WM + li;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) fa_off[kk][h] = (uint32_t)p2_arow_off(row, 4 * kk + 2 * lh + h);
-      const int brow = wn * WN + li;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) fb_off[kk] = (uint32_t)(kP2AStage + plane_off(brow, 2 * kk + lh));
-    }
+    const C1FragOff fo = c1_frag_off<BN>(wm * WM + li, wn * WN + li, lh);
     // staging offsets of this lane's accumulator quads: chunk = wn * 16 + b * 8 + (2 r4 + lh); block b is a 128-byte immediate
     uint32_t st_off[4];
 #pragma unroll
     for (int r4 = 0; r4 < 4; ++r4) st_off[r4] = stg0 + p2_out_off(wm * WM + li, wn * 16 + 2 * r4 + lh);
 
-    float a_inv, out_scale, bias_max = 0.f;
-    {
-      const OpScale sa = op_scale(act_absmax(p.a_scale)), sw = op_scale(*p.w_scale);
-      a_inv = sa.inv;
-      out_scale = sa.s * sw.s;
-      if (p.bias != nullptr && p.out_amax != nullptr) {   // max |bias| over this column tile, the same in every lane
-        const int c0 = n0 + 2 * lane;
-        float m = 0.f;
-        if (c0 < p.Cd) m = fabsf(p.bias[c0]);
-        if (c0 + 1 < p.Cd) m = fmaxf(m, fabsf(p.bias[c0 + 1]));
+    const C1Scale sc = c1_scale(act_absmax(p.a_scale), *p.w_scale);
+    float bias_max = 0.f;
+    if (p.bias != nullptr && p.out_amax != nullptr) {   // max |bias| over this column tile, the same in every lane
+      const int c0 = n0 + 2 * lane;
+      float m = 0.f;
+      if (c0 < p.Cd) m = fabsf(p.bias[c0]);
+      if (c0 + 1 < p.Cd) m = fmaxf(m, fabsf(p.bias[c0 + 1]));
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        bias_max = m;
-      }
+      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+      bias_max = m;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    f32x16 acc[NB];
+    f32x16 acc1[1][NB];              // (the [row block][column block] form C1Frag::mma takes; one row block here)
+    f32x16 (&acc)[NB] = acc1[0];
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
 
-    struct Frag {
-      u32x4 a0, a1;            // raw activation words: 8 consecutive k of this lane's row
-      bf16x8 b[NB][2];         // weight planes h, l
-    };
+    using Frag = C1Frag<NB>;
     auto read_frag = [&](uint32_t S, int kk, Frag& f) {
       if (EVK_PS2_ABL & 128) {       // (ablation: no fragment reads — the registers keep whatever they hold, made opaque)
-        asm volatile("" : "+v"(f.a0), "+v"(f.a1));
+        asm volatile("" : "+v"(f.a[0][0]), "+v"(f.a[0][1]));
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
           for (int pt = 0; pt < 2; ++pt) asm volatile("" : "+v"(f.b[b][pt]));
         return;
       }
-#pragma unroll
-      for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int pt = 0; pt < 2; ++pt)
-          f.b[b][pt] = __builtin_bit_cast(bf16x8, p2_lds_read16(S + fb_off[kk] + pt * kP2BPlane + b * 32 * kRowBytes));
-      f.a0 = p2_lds_read16(S + fa_off[kk][0]);
-      f.a1 = p2_lds_read16(S + fa_off[kk][1]);
+      f.template read<BN>(S, fo.a[kk], fo.b[kk]);
     };
-    auto mma = [&](const Frag& f) {
-      // (read as floats: a bit_cast of an ext-vector ELEMENT is miscompiled by this hipcc; conv1x1_dma.hip)
-      const f32x4 w0 = __builtin_bit_cast(f32x4, f.a0), w1 = __builtin_bit_cast(f32x4, f.a1);
-      u32x4 H, L;
-      uint32_t h, l, unused = 0;
-      if (EVK_PS2_ABL & 256) {       // (ablation: no operand split — the raw words go to the matrix pipe)
-        H = f.a0; L = f.a1;
-      } else {
-      split_op<2, PK>(w0.x, w0.y, a_inv, h, l, unused); H[0] = h; L[0] = l;
-      split_op<2, PK>(w0.z, w0.w, a_inv, h, l, unused); H[1] = h; L[1] = l;
-      split_op<2, PK>(w1.x, w1.y, a_inv, h, l, unused); H[2] = h; L[2] = l;
-      split_op<2, PK>(w1.z, w1.w, a_inv, h, l, unused); H[3] = h; L[3] = l;
-      }
-      const bf16x8 fa[2] = {__builtin_bit_cast(bf16x8, H), __builtin_bit_cast(bf16x8, L)};
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[b] = mfma_np<2>(f.b[b][kHB[t]], fa[kHA[t]], acc[b]);
-    };
+    // (ablation bit 256: no operand split — the raw words go to the matrix pipe)
+    auto mma = [&](const Frag& f) { f.template mma<PK, !(EVK_PS2_ABL & 256)>(acc1, sc.a_inv); };
     uint32_t amax_m = 0;
     auto park_tile = [&]() {           // accumulators -> staging image, then start the next tile from zero
       if (EVK_PS2_ABL & 32) {          // (ablation: keep the accumulators live without the LDS writes)
@@ -269,9 +179,9 @@ __global__ __launch_bounds__(64 * kP2Waves) void conv1x1_ps2_kernel(const IGemmA
       for (int b = 0; b < NB; ++b)
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
-          const f32x4 v = {acc[b][4 * r4] * out_scale, acc[b][4 * r4 + 1] * out_scale, acc[b][4 * r4 + 2] * out_scale,
-                           acc[b][4 * r4 + 3] * out_scale};
-          p2_lds_write16(st_off[r4] + b * 128, v);
+          const f32x4 v = {acc[b][4 * r4] * sc.out, acc[b][4 * r4 + 1] * sc.out, acc[b][4 * r4 + 2] * sc.out,
+                           acc[b][4 * r4 + 3] * sc.out};
+          lds_write16(st_off[r4] + b * 128, v);
           amax_m = max(amax_m, max(max(__builtin_bit_cast(uint32_t, v.x) & 0x7fffffffu, __builtin_bit_cast(uint32_t, v.y) & 0x7fffffffu),
                                    max(__builtin_bit_cast(uint32_t, v.z) & 0x7fffffffu, __builtin_bit_cast(uint32_t, v.w) & 0x7fffffffu)));
         }
@@ -286,7 +196,7 @@ __global__ __launch_bounds__(64 * kP2Waves) void conv1x1_ps2_kernel(const IGemmA
     uint32_t S_c = lds0;
     int kt = 0;
     if (!(EVK_PS2_ABL & 4)) read_frag(opaque(S_c), 0, fx);
-    // (the last global step is peeled: a conditional read behind the barrier would make hipcc wait for the reads just issued)
+    // (the last global step is peeled: c1_tile.hpp)
     for (int g = 0; g + 1 < G; ++g) {
       const uint32_t S = opaque(S_c);
       S_c = S_c == lds0 + (NST - 1) * kP2Stage ? lds0 : S_c + kP2Stage;
@@ -298,26 +208,13 @@ __global__ __launch_bounds__(64 * kP2Waves) void conv1x1_ps2_kernel(const IGemmA
         if (last_of_tile) park_tile();
         continue;
       }
-      read_frag(S, 1, fy);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(fx);
-      __builtin_amdgcn_sched_barrier(0);
-      p2_barrier();                                  // B(g): stage g + 1 has landed; fy returned long ago
-      read_frag(Sn, 0, fx);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(fy);
-      __builtin_amdgcn_sched_barrier(0);
+      c1_step(S, Sn, fx, fy, read_frag, mma, p2_barrier);   // its barrier is B(g)
       if (last_of_tile) park_tile();                   // complete at B(g + 1): ring_barrier waits for the ds_writes
     }
     if (EVK_PS2_ABL & 4) {
       p2_barrier();
     } else {
-      read_frag(opaque(S_c), 1, fy);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(fx);
-      __builtin_amdgcn_sched_barrier(0);
-      p2_barrier();                                  // B(G - 1)
-      mma(fy);
+      c1_last_step(opaque(S_c), fx, fy, read_frag, mma, p2_barrier);   // B(G - 1)
     }
     park_tile();
     p2_barrier();                                    // E1: the last tile is staged
@@ -357,10 +254,10 @@ __global__ __launch_bounds__(64 * kP2Waves) void conv1x1_ps2_kernel(const IGemmA
 
   auto lds_of = [&](int i) { return ((i & 1) ? ro_odd : ro_even) + (uint32_t)(i >> 1) * (8 * kP2OutRow); };
   auto drain = [&](int count) {                      // the next `count` instructions of this wave's tile half
-    f32x4 v = __builtin_bit_cast(f32x4, p2_lds_read16(lds_of(d_i)));
+    f32x4 v = __builtin_bit_cast(f32x4, lds_read16(lds_of(d_i)));
     for (int u = 0; u < count; ++u) {
       const int nx = d_i + 1 < kP2Instr ? d_i + 1 : d_i;
-      const f32x4 vn = __builtin_bit_cast(f32x4, p2_lds_read16(lds_of(nx)));
+      const f32x4 vn = __builtin_bit_cast(f32x4, lds_read16(lds_of(nx)));
       if (d_row < p.M && col_ok) {
         f32x4 t = v + bias;
         t.x = fmaxf(t.x, floor_v); t.y = fmaxf(t.y, floor_v); t.z = fmaxf(t.z, floor_v); t.w = fmaxf(t.w, floor_v);
@@ -465,15 +362,13 @@ int launch_conv1x1_ps2(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
   const int slots = device_cus_per_xcd() / a.tiles_n * a.tiles_n;
   EVK_REQUIRE(slots > 0, EVK_E_INVALID, "conv1x1_ps2: %d column tiles do not fit this device's CUs per XCD", a.tiles_n);
   const int grid = 8 * slots;
-  const unsigned long long sb = (unsigned long long)a.N * a.Hs * a.Ws * a.Cs * 4ull;
-  const unsigned long long wb = 2ull * a.Cd * a.Kpad * 2ull;
   const dim3 g((unsigned)grid), b(64 * kP2Waves);
   // non-temporal activation loads where at most two workgroups read a row tile (256 -> 256 @128^2 197 -> 187 us; with four
   // column tiles the hint loses: 128 -> 512 @64^2 51 -> 58)
   const int which = (a.a_packed ? 2 : 0) | (a.bn_part != nullptr ? 1 : 0) | (a.tiles_n <= 2 ? 4 : 0);
   auto go = [&](auto kern) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kP2Lds);
-    hipLaunchKernelGGL(kern, g, b, kP2Lds, stream, a, (uint32_t)sb, (uint32_t)wb);
+    hipLaunchKernelGGL(kern, g, b, kP2Lds, stream, a, (uint32_t)c1_src_bytes(a), (uint32_t)c1_wgt_bytes(a));
   };
   switch (which) {
     case 0: go(&conv1x1_ps2_kernel<false, false, false>); break;

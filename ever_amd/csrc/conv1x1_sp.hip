@@ -11,17 +11,14 @@
 // returns; and the streaming rate of LDS-DMA scales with the number of ISSUING waves (2 waves: 3.0 TB/s chip-wide at any
 // depth, 4: 5.8, 8: 7.1), not with the access pattern (128-byte row segments 4 KB apart = whole rows).  Hence:
 //  * the eight compute waves (4 x 2, 32 x BN/2 each) issue NO vector-memory instruction inside the K loop; four LOADER waves
-//    issue the whole ring (activation tile as raw 4-byte words in 128-byte rows, weights as their two fp16 planes in 64-byte
-//    rows, the XOR swizzles on the source side: the same LDS images as conv1x1_dma.hip) and absorb the queue's back-pressure;
-//  * the fragment registers are double-buffered ACROSS the barrier: a step is
-//        read k-half 1 | MFMAs of k-half 0 | barrier (stage kt+1 has landed) | read k-half 0 of stage kt+1 | MFMAs of k-half 1
-//    so every fragment read has a whole MFMA group (192 cycles) to return and the only wait left is the barrier itself; this
-//    needs stage kt+1 complete one half step early: ring of NST = 4 stages, NST - 1 in flight;
+//    issue the whole ring (the LDS image, its source offsets and fragment reads: c1_tile.hpp, shared with conv1x1_dma.hip)
+//    and absorb the queue's back-pressure;
+//  * the fragment registers are double-buffered ACROSS the barrier (c1_tile.hpp: c1_step); this needs stage kt+1 complete
+//    one half step early: ring of NST = 4 stages, NST - 1 in flight;
 //  * no run-time ablation switch inside the loop (compile-time EVK_SP_ABL: 1 no loader DMA, 4 no compute, 8 no stores).
 // Epilogues: the shared ones of igemm_common.hpp; the loader waves end before them (an ended wave is not waited for).
 #include "conv_route.hpp"
-#include "x3_common.hpp"
-#include "lds_dma.hpp"
+#include "c1_tile.hpp"
 #include <stdlib.h>
 #include <string.h>
 
@@ -33,30 +30,20 @@ namespace evk {
 
 namespace {
 
-constexpr int kSpRow = BK3 * 4;  // bytes of one activation row of a K step (32 four-byte words)
-constexpr int kSpCW = 8;         // compute waves
+constexpr int kSpCW = 8;   // compute waves
 
-__device__ __forceinline__ void sp_dma16s(i32x4 rsrc, uint32_t lds_byte, uint32_t voff, uint32_t soff) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds"
-               :: "v"(voff), "s"(lds_byte), "s"(rsrc), "s"(soff) : "memory", "m0");
-}
-__device__ __forceinline__ u32x4 sp_lds_read16(uint32_t lds_byte) {
-  return *(const __attribute__((address_space(3))) u32x4*)(uintptr_t)lds_byte;
-}
 // (ablations 16: no barrier; 32: the fragments are read once, in front of the loop; 64: no operand split / byte permutes)
 __device__ __forceinline__ void sp_barrier() { if (!(EVK_SP_ABL & 16)) ring_barrier(); }
-__device__ __forceinline__ int sp_arow_off(int row, int c) { return row * kSpRow + ((c ^ ((row >> 1) & 7)) << 4); }
 
 }  // namespace
 
 // LW loader waves (4); NST ring stages
 template <int BN, bool PK, int NST, int LW>
 __global__ __launch_bounds__(64 * (kSpCW + LW)) void conv1x1_sp_kernel(const IGemmArgs p, uint32_t src_bytes, uint32_t wgt_bytes) {
-  constexpr int BM = 128, WAVES_M = 4, WAVES_N = 2, WM = 32, WN = BN / 2, NB = WN / 32;
-  constexpr int kAStage = BM * kSpRow, kBPlane = BN * kRowBytes, kStage = kAStage + 2 * kBPlane;
-  constexpr int AI = kAStage / 1024 / LW;        // activation DMA instructions per loader wave and stage (8 rows each)
-  constexpr int BI = 2 * kBPlane / 1024 / LW;    // weight-plane DMA instructions per loader wave and stage
-  constexpr int PER = AI + BI;
+  constexpr int BM = kC1BM, WAVES_M = 4, WAVES_N = 2, WM = 32, WN = BN / 2, NB = WN / 32;
+  using St = C1Stage<BN>;
+  constexpr int kStage = St::bytes;
+  constexpr int AI = St::a_instr(LW), BI = St::b_instr(LW), PER = AI + BI;   // DMA instructions per loader wave and stage
   static_assert(LW == 4 && AI >= 1 && BI >= 1 && NB >= 1 && NST >= 3, "tile shape");
   static_assert((NST - 2) * PER <= 62, "vmcnt range");
 
@@ -74,41 +61,15 @@ __global__ __launch_bounds__(64 * (kSpCW + LW)) void conv1x1_sp_kernel(const IGe
     const int lw = wave - kSpCW;
     const i32x4 rs_a = make_rsrc(p.src, src_bytes), rs_b = make_rsrc(p.wgt3, wgt_bytes);
     uint32_t a_voff[AI], b_voff[BI];
-#pragma unroll
-    for (int t = 0; t < AI; ++t) {
-      const int row = 8 * (AI * lw + t) + (lane >> 3);    // row of the tile this lane's 16 bytes belong to
-      const int c = (lane & 7) ^ ((row >> 1) & 7);        // source chunk that lands on LDS chunk (lane & 7)
-      const int m = m0 + row;
-      uint32_t off = kDmaOOB;
-      if (m < p.M) {
-        const int hw = p.Hm * p.Wm;
-        const int n = m / hw;
-        const int rem = m - n * hw;
-        const int gy = rem / p.Wm;
-        const int gx = rem - gy * p.Wm;
-        const int sy = gy * p.ash + p.oy0, sx = gx * p.asw + p.ox0;
-        if ((unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws)
-          off = (uint32_t)(((n * p.Hs + sy) * p.Ws + sx) * p.Cs) * 4u + (uint32_t)c * 16u;
-      }
-      a_voff[t] = off;
-    }
-    const uint32_t plane_bytes = (uint32_t)p.Cd * (uint32_t)p.Kpad * 2u;
-#pragma unroll
-    for (int t = 0; t < BI; ++t) {
-      const int s = 64 * (BI * lw + t) + lane;  // 16-byte slot among the stage's 2 * BN * 4 weight slots
-      const int pt = s / (BN * 4);
-      const int row = (s - pt * BN * 4) >> 2;
-      const int c = (s & 3) ^ ((row >> 2) & 3);
-      const int co = n0 + row;
-      b_voff[t] = co < p.Cd ? (uint32_t)pt * plane_bytes + (uint32_t)co * (uint32_t)p.Kpad * 2u + (uint32_t)c * 16u : kDmaOOB;
-    }
+    c1_a_voff<AI>(p, m0, lw, lane, a_voff);
+    c1_b_voff<BN, BI>(p, n0, lw, lane, b_voff);
     auto issue = [&](int kt, uint32_t S) {
       if (EVK_SP_ABL & 1) return;
-      const uint32_t ka = (uint32_t)kt * kSpRow, kb = (uint32_t)kt * kRowBytes;
+      const uint32_t ka = c1_a_soff(kt), kb = c1_b_soff(kt);
 #pragma unroll
-      for (int t = 0; t < AI; ++t) sp_dma16s(rs_a, S + (AI * lw + t) * 1024, a_voff[t], ka);
+      for (int t = 0; t < AI; ++t) dma16s_loader(rs_a, S + (AI * lw + t) * 1024, a_voff[t], ka);
 #pragma unroll
-      for (int t = 0; t < BI; ++t) sp_dma16s(rs_b, S + kAStage + (BI * lw + t) * 1024, b_voff[t], kb);
+      for (int t = 0; t < BI; ++t) dma16s_loader(rs_b, S + St::a_bytes + (BI * lw + t) * 1024, b_voff[t], kb);
     };
     // prologue: stages 0 .. NST-2 in flight
 #pragma unroll
@@ -135,76 +96,26 @@ __global__ __launch_bounds__(64 * (kSpCW + LW)) void conv1x1_sp_kernel(const IGe
   // ==================================================================== compute waves
   const int li = lane & 31, lh = lane >> 5;
   const int wm = wave % WAVES_M, wn = wave / WAVES_M;
-  uint32_t fa_off[2][2], fb_off[2];   // fragment read offsets inside a stage (lane constants)
-  {
-    const int row = wm * WM + li;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) fa_off[kk][h] = (uint32_t)sp_arow_off(row, 4 * kk + 2 * lh + h);
-    const int brow = wn * WN + li;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) fb_off[kk] = (uint32_t)(kAStage + plane_off(brow, 2 * kk + lh));
-  }
-  float a_inv, out_scale;
-  {
-    const OpScale sa = op_scale(act_absmax(p.a_scale)), sw = op_scale(*p.w_scale);
-    a_inv = sa.inv;
-    out_scale = sa.s * sw.s;
-  }
+  const C1FragOff fo = c1_frag_off<BN>(wm * WM + li, wn * WN + li, lh);
+  const C1Scale sc = c1_scale(act_absmax(p.a_scale), *p.w_scale);
   f32x16 acc[1][NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[0][b][r] = 0.f;
 
-  struct Frag {
-    u32x4 a0, a1;            // raw activation words: 8 consecutive k of this lane's row
-    bf16x8 b[NB][2];         // weight planes h, l
-  };
-  auto read_frag_now = [&](uint32_t S, int kk, Frag& f) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int pt = 0; pt < 2; ++pt)
-        f.b[b][pt] = __builtin_bit_cast(bf16x8, sp_lds_read16(S + fb_off[kk] + pt * kBPlane + b * 32 * kRowBytes));
-    f.a0 = sp_lds_read16(S + fa_off[kk][0]);
-    f.a1 = sp_lds_read16(S + fa_off[kk][1]);
-  };
+  using Frag = C1Frag<NB>;
+  auto read_frag_now = [&](uint32_t S, int kk, Frag& f) { f.template read<BN>(S, fo.a[kk], fo.b[kk]); };
   auto read_frag = [&](uint32_t S, int kk, Frag& f) {
     if (!(EVK_SP_ABL & 32)) read_frag_now(S, kk, f);
   };
-  auto mma = [&](const Frag& f) {
-    // (read as floats: a bit_cast of an ext-vector ELEMENT is miscompiled by this hipcc; conv1x1_dma.hip)
-    const f32x4 w0 = __builtin_bit_cast(f32x4, f.a0), w1 = __builtin_bit_cast(f32x4, f.a1);
-    u32x4 H, L;
-    uint32_t h, l, unused = 0;
-    if (EVK_SP_ABL & 64) {
-      const bf16x8 fr[2] = {__builtin_bit_cast(bf16x8, f.a0), __builtin_bit_cast(bf16x8, f.a1)};
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[0][b] = mfma_np<2>(f.b[b][kHB[t]], fr[kHA[t]], acc[0][b]);
-      return;
-    }
-    split_op<2, PK>(w0.x, w0.y, a_inv, h, l, unused); H[0] = h; L[0] = l;
-    split_op<2, PK>(w0.z, w0.w, a_inv, h, l, unused); H[1] = h; L[1] = l;
-    split_op<2, PK>(w1.x, w1.y, a_inv, h, l, unused); H[2] = h; L[2] = l;
-    split_op<2, PK>(w1.z, w1.w, a_inv, h, l, unused); H[3] = h; L[3] = l;
-    const bf16x8 fa[2] = {__builtin_bit_cast(bf16x8, H), __builtin_bit_cast(bf16x8, L)};
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) acc[0][b] = mfma_np<2>(f.b[b][kHB[t]], fa[kHA[t]], acc[0][b]);
-  };
+  auto mma = [&](const Frag& f) { f.template mma<PK, !(EVK_SP_ABL & 64)>(acc, sc.a_inv); };
 
   Frag fx, fy;
   sp_barrier();                                     // P0: stage 0 has landed
   uint32_t S_c = lds0;
   if (!(EVK_SP_ABL & 4)) read_frag_now(opaque(S_c), 0, fx);
   if (EVK_SP_ABL & 32) read_frag_now(opaque(S_c), 1, fy);
-  // (the last step is peeled: a conditional read of the next stage would merge two LDS-counter states behind the barrier and
-  // make hipcc wait for the reads just issued — seen in the ISA as lgkmcnt(1) in front of the second MFMA group)
   for (int kt = 0; kt + 1 < nk; ++kt) {
     const uint32_t S = opaque(S_c);
     S_c = S_c == lds0 + (NST - 1) * kStage ? lds0 : S_c + kStage;
@@ -213,25 +124,12 @@ __global__ __launch_bounds__(64 * (kSpCW + LW)) void conv1x1_sp_kernel(const IGe
       sp_barrier();
       continue;
     }
-    read_frag(S, 1, fy);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(fx);
-    __builtin_amdgcn_sched_barrier(0);
-    sp_barrier();                                   // B(kt): stage kt + 1 has landed; fy has returned long ago
-    read_frag(Sn, 0, fx);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(fy);
-    __builtin_amdgcn_sched_barrier(0);
+    c1_step(S, Sn, fx, fy, read_frag, mma, sp_barrier);   // its barrier is B(kt)
   }
   if (EVK_SP_ABL & 4) {
     sp_barrier();
   } else {
-    read_frag(opaque(S_c), 1, fy);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(fx);
-    __builtin_amdgcn_sched_barrier(0);
-    sp_barrier();                                   // B(nk - 1): the loader waves' last barrier
-    mma(fy);
+    c1_last_step(opaque(S_c), fx, fy, read_frag, mma, sp_barrier);   // B(nk - 1)
   }
   if (EVK_SP_ABL & 8) {   // (every accumulator register stays live: nothing of the loop may be optimised away)
     float sum = 0.f;
@@ -242,7 +140,7 @@ __global__ __launch_bounds__(64 * (kSpCW + LW)) void conv1x1_sp_kernel(const IGe
     if (sum == 12345.f) p.dst[0] = 0.f;
     return;
   }
-  igemm_scale_acc<1, NB>(acc, out_scale);
+  igemm_scale_acc<1, NB>(acc, sc.out);
   if (p.bn_part) {
     __syncthreads();   // the ring becomes the statistics epilogue's scratch: every compute wave is done reading the last stage
     igemm_epilogue_stats<1, NB, WM, WN, WAVES_M, WAVES_N>(p, acc, m0, n0, wm, wn, li, lh, reinterpret_cast<float*>(smem_sp));
@@ -255,28 +153,8 @@ __global__ __launch_bounds__(64 * (kSpCW + LW)) void conv1x1_sp_kernel(const IGe
 
 template <int BN, bool PK, int NST>
 static int launch_sp(IGemmArgs& a, hipStream_t stream) {
-  constexpr int BM = 128, LW = 4;
-  a.tiles_m = ceil_div(a.M, BM);
-  a.tiles_n = ceil_div(a.Cd, BN);
-  bn_stats_setup(a, BM, BN, 4, a.tiles_m);
-  size_t lds = (size_t)NST * (BM * kSpRow + 2 * BN * kRowBytes);
-  const size_t scratch = ((size_t)2 * 4 * 32 * (BN / 2 + 4) + (size_t)3 * 2 * 3 * (BN / 2)) * sizeof(float);
-  if (lds < scratch) lds = scratch;
-  static PerDeviceOnce attr_once;
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_sp_kernel<BN, PK, NST, LW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  const long long nwg = (long long)a.tiles_m * a.tiles_n;
-  if (nwg <= 0 || nwg > 0x7fffffffLL) {
-    set_error("conv1x1_sp: bad grid %lld", nwg);
-    return EVK_E_INVALID;
-  }
-  const unsigned long long sb = (unsigned long long)a.N * a.Hs * a.Ws * a.Cs * 4ull;
-  const unsigned long long wb = 2ull * a.Cd * a.Kpad * 2ull;
-  hipLaunchKernelGGL((conv1x1_sp_kernel<BN, PK, NST, LW>), dim3((unsigned)nwg), dim3(64 * (kSpCW + LW)), lds, stream, a, (uint32_t)sb,
-                     (uint32_t)wb);
-  return check_launch("conv1x1_sp");
+  constexpr int LW = 4;
+  return launch_c1_ring<&conv1x1_sp_kernel<BN, PK, NST, LW>, BN, NST>(a, stream, 64 * (kSpCW + LW), 4, "conv1x1_sp");
 }
 
 bool conv1x1_sp_supports(const IGemmArgs& a) { return conv1x1_dma_supports(a) && a.Kpad / BK3 >= 2; }

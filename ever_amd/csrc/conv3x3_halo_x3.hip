@@ -188,11 +188,7 @@ __global__ __launch_bounds__(256 + 64 * MW) void conv3x3_halo_x3_kernel(const IG
         const uint32_t soff = (uint32_t)(jy * 3) * tap_bytes + (uint32_t)c * (uint32_t)p.Cd * kRB;
         const uint32_t S = ldsB + stage * kBStage;
 #pragma unroll
-        for (int i = 0; i < PERB; ++i) {
-          uint32_t keep;
-          asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                       : "=&s"(keep) : "v"(bd_voff[i]), "s"(S + bd_lds[i]), "s"(rs_b), "s"(soff) : "memory");
-        }
+        for (int i = 0; i < PERB; ++i) dma16s(rs_b, S + bd_lds[i], bd_voff[i], soff);
       };
       issue_b(0, 0);
       if (niter > 1) issue_b(1, 1);

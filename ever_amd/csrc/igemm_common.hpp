@@ -309,7 +309,11 @@ __device__ __forceinline__ void bn_part_write(const IGemmArgs& p, const BnLaneSt
 }
 
 // the row-linear kernels' epilogue in statistics mode (dense destination, Cd % 4 == 0, whole column blocks).
-// scratch_base: LDS area of (waves x 32 x (WN + 4) + WAVES_N x 3 x WN) floats, free of other use
+// scratch_base: LDS area of igemm_stats_scratch_bytes, free of other use — every wave's 32 x (WN + 4) transpose block, then
+// bn_part_write's exchange area (three parked row waves at the most)
+constexpr size_t igemm_stats_scratch_bytes(int waves_m, int waves_n, int wn) {
+  return ((size_t)waves_m * waves_n * 32 * (wn + 4) + (size_t)3 * waves_n * 3 * wn) * sizeof(float);
+}
 template <int MB, int NB, int WM, int WN, int WAVES_M, int WAVES_N>
 __device__ __forceinline__ void igemm_epilogue_stats(const IGemmArgs& p, f32x16 (&acc)[MB][NB], int m0, int n0, int wm, int wn,
                                                      int li, int lh, float* scratch_base) {

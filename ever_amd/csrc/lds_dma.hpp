@@ -1,5 +1,6 @@
 // Global -> LDS by DMA (`buffer_load_dwordx4 ... offen lds`), hand-counted completion, raw barrier: shared by the kernels
-// whose operands reach LDS without a VGPR round trip (conv_wgrad_tr.hip, conv1x1_dma.hip).
+// whose operands reach LDS without a VGPR round trip (conv_wgrad_tr.hip, the one-tap kernels of c1_tile.hpp, the weight
+// rings of conv3x3_halo_x3.hip / conv3x3_wino_x3.hip).
 #pragma once
 #include "common.hpp"
 
@@ -21,6 +22,26 @@ __device__ __forceinline__ void dma16(i32x4 rsrc, uint32_t lds_byte, uint32_t vo
   uint32_t keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
+}
+// The same with a scalar byte offset on top of the per-lane one (a K step; not part of the range check, so an out-of-range
+// lane offset stays out of range).  Two forms, because M0 is also what the compiler's own LDS instructions read: a wave
+// that reads fragments as well as issuing DMA (the symmetric rings, the 3x3 staging waves) must hand M0 back — dma16s; a
+// loader wave issues no other M0 user, so dma16s_loader leaves M0 clobbered and saves two scalar moves per instruction.
+// NT: the non-temporal hint (conv1x1_ps2.hip decides per launch).
+__device__ __forceinline__ void dma16s(i32x4 rsrc, uint32_t lds_byte, uint32_t voff, uint32_t soff) {
+  uint32_t keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(voff), "s"(lds_byte), "s"(rsrc), "s"(soff) : "memory");
+}
+template <bool NT = false>
+__device__ __forceinline__ void dma16s_loader(i32x4 rsrc, uint32_t lds_byte, uint32_t voff, uint32_t soff) {
+  if constexpr (NT) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen nt lds"
+                 :: "v"(voff), "s"(lds_byte), "s"(rsrc), "s"(soff) : "memory", "m0");
+  } else {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds"
+                 :: "v"(voff), "s"(lds_byte), "s"(rsrc), "s"(soff) : "memory", "m0");
+  }
 }
 // makes a value opaque to the optimiser: without it the loop-invariant (lane constant + immediate) sums of all the
 // fragment addresses are hoisted out of the step loop into as many VGPRs (spills) instead of one base + offset fields

@@ -20,6 +20,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
                                  dict(EVK_TUNE='1', EVK_X3_FORCE='t64'),            # ... ring of three, 64-wide tiles
                                  dict(EVK_TUNE='1', EVK_X3_FORCE='e64'),            # ... 64-wide tiles
                                  dict(EVK_TUNE='1', EVK_X3_FORCE='d256'),           # three-stage ring, 256-wide tiles
+                                 dict(EVK_TUNE='1', EVK_X3_FORCE='d128'),           # ... 128-wide tiles
+                                 dict(EVK_TUNE='1', EVK_X3_FORCE='d64'),            # ... 64-wide tiles
+                                 dict(EVK_TUNE='1', EVK_X3_FORCE='s64'),            # loader-wave form, ring of four, 64-wide tiles
+                                 dict(EVK_TUNE='1', EVK_X3_FORCE='t128'),           # loader-wave form, ring of three, 128-wide tiles
                                  dict(EVK_C1_DMA='0')],                             # the register-staged kernels, same checks
                          ids=lambda e: '-'.join(e.values()))
 def test_dma_one_tap_convolution_matches_torch(cuda, env):
