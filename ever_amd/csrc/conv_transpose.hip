@@ -8,7 +8,7 @@
 // Every entry point takes the descriptor `d` of C: (N, H, W, Cin) = the transposed convolution's OUTPUT size and channel
 // count, (Ho, Wo, Cout) = its INPUT.  Nothing here is a new kernel: the reference's path has no transposed convolution
 // (SURVEY 2.3), BASELINE.json's north_star names it, and the strided data-gradient already is it.
-#include "common.hpp"
+#include "wgrad_common.hpp"
 
 namespace evk {
 
@@ -19,9 +19,6 @@ __global__ void bias_rows_kernel(float* __restrict__ y, const float* __restrict_
   v += reinterpret_cast<const f32x4*>(bias)[i % c4];
   reinterpret_cast<f32x4*>(y)[i] = v;
 }
-
-int launch_colsum(const float* src, float* out, int64_t rows, int c, float* workspace, hipStream_t st);  // conv_wgrad.hip
-size_t colsum_workspace_bytes(int64_t rows, int c);
 
 static int add_bias(const evk_conv_desc* d, float* y, const float* bias, hipStream_t st) {
   if (!bias) return EVK_OK;

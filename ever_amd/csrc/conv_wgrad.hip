@@ -1,182 +1,19 @@
-// Convolution weight gradient for gfx950 on v_mfma_f32_32x32x2_f32.
+// What the weight-gradient family shares on the host, and the small kernels that finish its work:
 //
 //   dw[co][k] = sum_m dy[m][co] * im2col(x)[m][k]        m = (n, oy, ox),  k = (ky, kx, ci)
 //
-// Replaces aten::convolution_backward(weight, bias) of the nn.Conv2d sites listed in
-// conv_igemm.hip (reference ever/module/_resnets.py:21-29,149 ; fpn.py ; fs_relation.py).
-//
-// GEMM view: rows = Cout, cols = kh*kw*Cin, reduction = pixels.  Both operands are stored
-// pixel-major in HBM ([pixel][channel]), which is exactly the k-major LDS image the f32 MFMA
-// fragments want (lane l reads row k=l>>5, column i=l&31: 32 consecutive words, conflict free),
-// so tiles are staged [32 pixels][BM or BN channels] without any transpose.  The pixel range is
-// split across workgroups (grid.z); partial tiles go to the caller's workspace and are summed in a
-// fixed order by a second kernel => bitwise reproducible, no atomics.
+//   plan_wgrad / route_wgrad   tile, pixel split and THE decision which kernel a launch takes:
+//                              conv_wgrad_f32.hip (fp32 MFMA), conv_wgrad_x3.hip / conv_wgrad_x3ws.hip (split operands, staged
+//                              through registers), conv_wgrad_tr.hip (planar f16x2 operands by LDS DMA)
+//   wgrad_kernel_name          the route as a kernel trace spells it (evk_conv2d_wgrad_route)
+//   splitk_reduce              sums the splits' partial tiles in a fixed order
+//   colsum_partial / _final    column sums of dy: the bias gradient (also conv_transpose.hip's)
+//   conv_wgrad_any             arguments, launch, reduce, bias gradient; the extern "C" entry points
+// The device pieces the kernels share are in wgrad_tile.hpp.
 #include "wgrad_common.hpp"
 #include <stdlib.h>
 
 namespace evk {
-
-template <int BM, int BN, int WAVES_M, int WAVES_N>
-__global__ __launch_bounds__(256) void conv_wgrad_kernel(const WGradArgs p) {
-  constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
-  constexpr int MB = WM / 32, NB = WN / 32;
-  constexpr int ACH = BM / 4, BCH = BN / 4;          // 16-byte chunks per staged row
-  constexpr int APASS = BKP * ACH / 256, BPASS = BKP * BCH / 256;
-  constexpr int AROWS = 256 / ACH, BROWS = 256 / BCH;  // rows covered per pass
-  static_assert(WAVES_M * WAVES_N == 4, "4 waves");
-  static_assert(MB <= 2 && NB <= 2, "fragment vectors are float or float2");
-  struct alignas(4 * MB) FragA { float v[MB]; };
-  struct alignas(4 * NB) FragB { float v[NB]; };
-
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                   // [2][32][BM]
-  float* Bs = smem + 2 * BKP * BM;    // [2][32][BN]
-
-  // XCD-aware order: all (co, k) tiles of one pixel chunk z run on the same XCD, so the chunk's dy / x
-  // rows are fetched into ONE L2 instead of eight (PMC: 3.4x the algorithmic bytes with the default order)
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int ntile = p.tiles_co * p.tiles_k;
-  const int z = bid / ntile;
-  const int tile = bid - z * ntile;
-  const int tile_k = tile % p.tiles_k;
-  const int tile_co = tile / p.tiles_k;
-  const int co0 = tile_co * BM, k0 = tile_k * BN;
-  const int pbeg = z * p.chunk;
-  const int pend = min(p.M, pbeg + p.chunk);
-
-  const int tid = threadIdx.x;
-  // A staging: dy rows
-  const int a_c = tid % ACH, a_r = tid / ACH;
-  const bool a_cvalid = (co0 + a_c * 4) < p.Cout;
-  // B staging: im2col rows; this thread's K chunk is fixed for the whole reduction
-  const int b_c = tid % BCH, b_r = tid / BCH;
-  const int q = (k0 >> 2) + b_c;
-  const bool b_cvalid = q * 4 < p.Ktot;
-  int b_dy = 0, b_dx = 0, b_cc = 0;
-  if (b_cvalid) {
-    const int tap = q / p.cpt;
-    b_cc = (q - tap * p.cpt) * 4;
-    const int ky = tap / p.kw, kx = tap - ky * p.kw;
-    b_dy = ky * p.dh - p.ph;
-    b_dx = kx * p.dw - p.pw;
-  }
-
-  f32x4 ra[APASS], rb[BPASS];
-  uint32_t okmask = 0;  // bit j: A pass j valid; bit 16+j: B pass j valid
-
-  // Branch-free gathers: every load is issued from a clamped (valid) 32-bit element offset; the
-  // zero-fill select is applied when the chunk is written to LDS (after the MFMA block), so the
-  // prefetch stays in flight under the MFMAs.
-  auto load_tiles = [&](int pix0) {
-    okmask = 0;
-#pragma unroll
-    for (int j = 0; j < APASS; ++j) {
-      const int m = pix0 + a_r + j * AROWS;
-      const bool ok = a_cvalid && m < pend;
-      okmask |= ok ? (1u << j) : 0u;
-      ra[j] = *reinterpret_cast<const f32x4*>(p.dy + (ok ? m * p.Cout + co0 + a_c * 4 : 0));
-    }
-#pragma unroll
-    for (int j = 0; j < BPASS; ++j) {
-      const int m = pix0 + b_r + j * BROWS;
-      const uint32_t mm = (uint32_t)min(m, p.M - 1);
-      const uint32_t n = fdiv(mm, p.fd_hw);
-      const uint32_t rem = mm - n * p.fd_hw.div;
-      const uint32_t oy = fdiv(rem, p.fd_w);
-      const uint32_t ox = rem - oy * p.fd_w.div;
-      const int sy = (int)oy * p.sh + b_dy;
-      const int sx = (int)ox * p.sw + b_dx;
-      const bool ok = b_cvalid && m < pend && (unsigned)sy < (unsigned)p.H && (unsigned)sx < (unsigned)p.W;
-      okmask |= ok ? (1u << (16 + j)) : 0u;
-      rb[j] = *reinterpret_cast<const f32x4*>(p.x + (ok ? (((int)n * p.H + sy) * p.W + sx) * p.Cin + b_cc : 0));
-    }
-  };
-  auto store_tiles = [&](int buf) {
-    float* Ab = As + buf * BKP * BM;
-    float* Bb = Bs + buf * BKP * BN;
-#pragma unroll
-    for (int j = 0; j < APASS; ++j) {
-      const bool ok = (okmask >> j) & 1u;
-      f32x4 v = ra[j];
-      v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-      *reinterpret_cast<f32x4*>(Ab + (a_r + j * AROWS) * BM + a_c * 4) = v;
-    }
-#pragma unroll
-    for (int j = 0; j < BPASS; ++j) {
-      const bool ok = (okmask >> (16 + j)) & 1u;
-      f32x4 v = rb[j];
-      v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-      *reinterpret_cast<f32x4*>(Bb + (b_r + j * BROWS) * BN + b_c * 4) = v;
-    }
-  };
-
-  const int wave = tid >> 6, lane = tid & 63;
-  const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-  const int li = lane & 31, lh = lane >> 5;
-
-  f32x16 acc[MB][NB];
-#pragma unroll
-  for (int a = 0; a < MB; ++a)
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  const int nk = (pend - pbeg + BKP - 1) / BKP;
-  if (nk > 0) {
-    load_tiles(pbeg);
-    store_tiles(0);
-  }
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) load_tiles(pbeg + (kt + 1) * BKP);
-    // Fragment reads: the wave's 64 (or 32) tile rows are dealt to (MFMA block a, lane row i) as
-    // row = MB*i + a, so ONE ds_read_b64 per operand feeds both blocks of a k-step, and the reads of
-    // step s+1 are issued before the MFMAs of step s (register double buffer) to hide LDS latency.
-    const float* Ab = As + buf * BKP * BM + wm * WM + MB * li;
-    const float* Bb = Bs + buf * BKP * BN + wn * WN + NB * li;
-    FragA fa_cur = *reinterpret_cast<const FragA*>(Ab + lh * BM);
-    FragB fb_cur = *reinterpret_cast<const FragB*>(Bb + lh * BN);
-#pragma unroll
-    for (int s = 0; s < BKP / 2; ++s) {
-      FragA fa_nxt = fa_cur;
-      FragB fb_nxt = fb_cur;
-      if (s + 1 < BKP / 2) {
-        fa_nxt = *reinterpret_cast<const FragA*>(Ab + (2 * s + 2 + lh) * BM);
-        fb_nxt = *reinterpret_cast<const FragB*>(Bb + (2 * s + 2 + lh) * BN);
-      }
-#pragma unroll
-      for (int a = 0; a < MB; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa_cur.v[a], fb_cur.v[b], acc[a][b], 0, 0, 0);
-      fa_cur = fa_nxt;
-      fb_cur = fb_nxt;
-      // pin the issue order: this step's (prefetch) LDS reads first, then its MFMAs -> the reads'
-      // latency is covered by MB*NB MFMAs (>= 256 cycles) instead of being waited for at once
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, MB * NB, 0);
-    }
-    if (kt + 1 < nk) store_tiles(buf ^ 1);
-    __syncthreads();
-  }
-
-  float* out = p.out + (size_t)z * p.Cout * p.Ktot;
-#pragma unroll
-  for (int a = 0; a < MB; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = co0 + wm * WM + MB * ((r & 3) + 8 * (r >> 2) + 4 * lh) + a;
-      if (row >= p.Cout) continue;
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const int col = k0 + wn * WN + NB * li + b;
-        if (col < p.Ktot) out[(size_t)row * p.Ktot + col] = acc[a][b][r];
-      }
-    }
-}
 
 #ifndef EVK_SK_NT
 #define EVK_SK_NT 1   // (528.2 -> 528.6 tiles/s over three interleaved rounds: inside the noise, kept as the right hint)
@@ -331,15 +168,6 @@ static int colsum_blocks(int64_t rows) {
   return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N>
-static int launch_wgrad(const WGradArgs& a, hipStream_t stream) {
-  const size_t lds = (size_t)2 * BKP * (BM + BN) * sizeof(float);
-  hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, WAVES_M, WAVES_N>), dim3(a.tiles_co * a.tiles_k * a.splitk),
-                     dim3(256), lds, stream, a);
-  return check_launch("conv_wgrad");
-}
-
-// column sums of a [rows][c] fp32 matrix (bias gradients): also used by conv_transpose.hip
 size_t colsum_workspace_bytes(int64_t rows, int c) { return (size_t)colsum_blocks(rows) * c * sizeof(float) + 256; }
 int launch_colsum(const float* src, float* out, int64_t rows, int c, float* workspace, hipStream_t st) {
   const int nblk = colsum_blocks(rows);
@@ -453,11 +281,7 @@ static int conv_wgrad_any(const evk_conv_desc* d, const float* x, const float* d
     case WGradKernel::Tr: rc = launch_wgrad_tr(a, route, st); break;
     case WGradKernel::X3:
     case WGradKernel::X3Ws: rc = launch_wgrad_x3(a, route, st); break;
-    default:
-      if (pl.bm == 128 && pl.bn == 128) rc = launch_wgrad<128, 128, 2, 2>(a, st);
-      else if (pl.bm == 64 && pl.bn == 128) rc = launch_wgrad<64, 128, 2, 2>(a, st);
-      else if (pl.bm == 128 && pl.bn == 64) rc = launch_wgrad<128, 64, 2, 2>(a, st);
-      else rc = launch_wgrad<64, 64, 2, 2>(a, st);
+    default: rc = launch_wgrad_f32(a, route, st);
   }
   if (rc) return rc;
   if (pl.splitk > 1) {
@@ -473,17 +297,7 @@ static int conv_wgrad_any(const evk_conv_desc* d, const float* x, const float* d
     rc = check_launch("splitk_reduce");
     if (rc) return rc;
   }
-  if (dbias) {
-    const int64_t rows = a.M;
-    const int nblk = colsum_blocks(rows);
-    const int64_t rpb = (rows + nblk - 1) / nblk;
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(nblk), dim3(256), 0, st, dy, (float*)workspace, rows, d->Cout, rpb);
-    rc = check_launch("colsum_partial");
-    if (rc) return rc;
-    hipLaunchKernelGGL(colsum_final_kernel, dim3((d->Cout + 7) / 8), dim3(256), 0, st, (const float*)workspace,
-                       dbias, nblk, d->Cout);
-    rc = check_launch("colsum_final");
-  }
+  if (dbias) rc = launch_colsum(dy, dbias, a.M, d->Cout, (float*)workspace, st);
   return rc;
 }
 
@@ -513,7 +327,7 @@ extern "C" int evk_conv2d_wgrad_f16x2_ex(const evk_conv_desc* d, const void* x, 
                                          size_t workspace_bytes, uint32_t flags, void* stream) {
   EVK_REQUIRE(d && d->Cin % 4 == 0 && d->Cout % 4 == 0, EVK_E_UNSUPPORTED, "conv2d_wgrad_f16x2_ex: channels must be multiples of 4");
   EVK_REQUIRE(x_absmax && dy_absmax, EVK_E_INVALID, "conv2d_wgrad_f16x2_ex: null scales");
-  EVK_REQUIRE((flags & ~(EVK_CONV_X_PACKED | EVK_CONV_DY_PACKED | EVK_CONV_X_PLANAR | EVK_CONV_DY_PLANAR | EVK_CONV_WGRAD_SHARED)) == 0, EVK_E_INVALID,
+  EVK_REQUIRE((flags & ~kWGradFlags) == 0, EVK_E_INVALID,
               "conv2d_wgrad_f16x2_ex: unknown flag 0x%x", flags);
   return conv_wgrad_any(d, reinterpret_cast<const float*>(x), reinterpret_cast<const float*>(dy), dw, dbias, workspace,
                         workspace_bytes, stream, 1, 2, x_absmax, dy_absmax, flags);
@@ -532,7 +346,7 @@ extern "C" int evk_conv2d_wgrad_route(const evk_conv_desc* d, int32_t planes, ui
   EVK_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->kh > 0 && d->kw > 0 && d->stride_h > 0 &&
                   d->stride_w > 0 && d->dil_h > 0 && d->dil_w > 0 && d->Cin > 0 && d->Cout > 0,
               EVK_E_INVALID, "conv2d_wgrad_route: bad descriptor");
-  EVK_REQUIRE((flags & ~(EVK_CONV_X_PACKED | EVK_CONV_DY_PACKED | EVK_CONV_X_PLANAR | EVK_CONV_DY_PLANAR | EVK_CONV_WGRAD_SHARED)) == 0,
+  EVK_REQUIRE((flags & ~kWGradFlags) == 0,
               EVK_E_INVALID, "conv2d_wgrad_route: unknown flag 0x%x", flags);
   buf[0] = 0;
   WGradRoute r;

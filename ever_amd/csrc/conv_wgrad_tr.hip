@@ -25,17 +25,11 @@
 //    taps — a tap is a whole-row offset of the transposing read — so the im2col operand is fetched 3.2 rows instead
 //    of 9 per step, and a step carries 27 MFMAs per k-half and wave instead of 12 (tile 128 co x 9 taps x 64 ci).
 //    NT = 1: tile 128 co x 256 k columns as four independent 64-channel segments (any kernel / stride / dilation).
-#include "wgrad_common.hpp"
-#include "x3_common.hpp"
+#include "wgrad_tile.hpp"
 #include "lds_dma.hpp"
 #include <stdlib.h>
 
-#ifndef EVK_WG_ABL
-#define EVK_WG_ABL 0   // timing ablations (tools/build_variant.sh -DEVK_WG_ABL=n; wrong results): 1 no loads, 2 no split / LDS writes,
-#endif                 // 4 no fragment reads / MFMAs, 8 no stores
 namespace evk {
-constexpr int kWgAbl = EVK_WG_ABL;
-
 
 namespace {
 
@@ -81,17 +75,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_tr_kernel(const WGradArgs p) {
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_tr[];
 
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int ntile = p.tiles_co * p.tiles_k;
-  const int z = bid / ntile;
-  const int tile = bid - z * ntile;
-  const int tile_k = tile % p.tiles_k;
-  const int tile_co = tile / p.tiles_k;
-  const int co0 = tile_co * G::BM;
-  const int k0 = tile_k * (NT == 9 ? 64 : 256);   // NT = 9: first input channel of the tile; NT = 1: first k column
-  const int pbeg = z * p.chunk;
-  const int pend = min(p.M, pbeg + p.chunk);
-  const int nk = (pend - pbeg + BKP - 1) / BKP;
+  // NT = 9: k0 is the first input channel of the tile (64 per tile index); NT = 1: the first k column
+  const WGradTile tl(p, G::BM, NT == 9 ? 64 : 256);
+  const int z = tl.z, co0 = tl.co0, k0 = tl.k0, pbeg = tl.pbeg;
+  WGRAD_PIXEL_RANGE(p, pbeg);
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
 
   // ------------------------------------------------------------------ this wave's share of a step's DMA
@@ -154,11 +141,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_tr_kernel(const WGradArgs p) {
     const int m0 = pbeg + kt * BKP;
     // the step's first pixel (wave-uniform).  NT = 9: the whole step lies in this image row; NT = 1: an octet does
     // (a step starts at a multiple of 32 pixels, Wo % 8 == 0 is the launcher's condition)
-    const uint32_t mm0 = (uint32_t)min(m0, p.M - 1);
-    const uint32_t n0 = fdiv(mm0, p.fd_hw);
-    const uint32_t rem0 = mm0 - n0 * p.fd_hw.div;
-    const uint32_t oy0 = fdiv(rem0, p.fd_w);
-    const int ox0 = (int)(rem0 - oy0 * p.fd_w.div);
+    const WGradPix px0(p, m0);
+    const int n0 = px0.n, oy0 = px0.oy, ox0 = px0.ox;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       const int mo = m0 + 8 * d_oc[i];
@@ -166,24 +150,20 @@ __global__ __launch_bounds__(512) void conv_wgrad_tr_kernel(const WGradArgs p) {
         const uint32_t off = (d_ok[i] && mo + drow < pend) ? (uint32_t)mo * (uint32_t)p.Cout * 2u + d_base[i] + a_lane : kOOBtr;
         dma16(rs_dy, S + (uint32_t)d_dst[i], off);
       } else if (NT == 9) {
-        const int sy = (int)oy0 + d_a[i], hs = 8 * d_oc[i] + drow, sx = ox0 - 1 + hs;
+        const int sy = oy0 + d_a[i], hs = 8 * d_oc[i] + drow, sx = ox0 - 1 + hs;
         const bool rowok = m0 < pend && (unsigned)sy < (unsigned)p.H;                     // scalar
-        const uint32_t sb = (uint32_t)((((int)n0 * p.H + sy) * p.W + ox0 - 1 + 8 * d_oc[i]) * p.Cin) * 2u + d_base[i];   // scalar
+        const uint32_t sb = (uint32_t)(((n0 * p.H + sy) * p.W + ox0 - 1 + 8 * d_oc[i]) * p.Cin) * 2u + d_base[i];   // scalar
         const uint32_t off = (rowok && hs < 34 && (unsigned)sx < (unsigned)p.W) ? sb + b_lane : kOOBtr;
         dma16(rs_x, S + (uint32_t)d_dst[i], off);
       } else {
-        uint32_t n = n0, oy = oy0;
-        int ox = ox0 + 8 * d_oc[i];
+        int n = n0, oy = oy0, ox = ox0 + 8 * d_oc[i];
         if (ox >= p.Wo) {                                        // the step wrapped into the next image row(s): scalar branch
-          const uint32_t mm = (uint32_t)min(mo, p.M - 1);
-          n = fdiv(mm, p.fd_hw);
-          const uint32_t rem = mm - n * p.fd_hw.div;
-          oy = fdiv(rem, p.fd_w);
-          ox = (int)(rem - oy * p.fd_w.div);
+          const WGradPix px(p, mo);
+          n = px.n; oy = px.oy; ox = px.ox;
         }
-        const int sy = (int)oy * p.sh + d_a[i], sxb = ox * p.sw + d_b[i];
+        const int sy = oy * p.sh + d_a[i], sxb = ox * p.sw + d_b[i];
         const bool rowok = d_ok[i] && (unsigned)sy < (unsigned)p.H;                       // scalar
-        const uint32_t sb = (uint32_t)((((int)n * p.H + sy) * p.W + sxb) * p.Cin) * 2u + d_base[i];   // scalar
+        const uint32_t sb = (uint32_t)(((n * p.H + sy) * p.W + sxb) * p.Cin) * 2u + d_base[i];   // scalar
         const int sx = sxb + drow * p.sw;
         const uint32_t off = (rowok && mo + drow < pend && (unsigned)sx < (unsigned)p.W) ? sb + b_lane : kOOBtr;
         dma16(rs_x, S + (uint32_t)d_dst[i], off);
@@ -304,20 +284,19 @@ bool wgrad_tr_nine_tap(const evk_conv_desc* d) {
 }
 
 template <int NT>
-static int launch_tr(const WGradArgs& b, hipStream_t stream) {
+static int launch_tr(const WGradArgs& a, hipStream_t stream) {
   const size_t lds = (size_t)3 * TrGeom<NT>::kStage;
   static PerDeviceOnce attr_once;
   if (attr_once.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_tr_kernel<NT>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
-  hipLaunchKernelGGL((conv_wgrad_tr_kernel<NT>), dim3(b.tiles_co * b.tiles_k * b.splitk), dim3(512), lds, stream, b);
+  hipLaunchKernelGGL((conv_wgrad_tr_kernel<NT>), dim3(a.tiles_co * a.tiles_k * a.splitk), dim3(512), lds, stream, a);
   return check_launch("conv_wgrad_tr");
 }
 
 int launch_wgrad_tr(const WGradArgs& a, const WGradRoute& r, hipStream_t stream) {
-  WGradArgs b = a;
-  return r.nt == 9 ? launch_tr<9>(b, stream) : launch_tr<1>(b, stream);
+  return r.nt == 9 ? launch_tr<9>(a, stream) : launch_tr<1>(a, stream);
 }
 
 // ---- stand-alone producers of the planar form (the fused ones are the BatchNorm passes' planar modes)

@@ -15,8 +15,7 @@
 // consecutive rows = distinct bank slots; the epilogue undoes the permutation.  Threads 0..BM-1 stage dy,
 // threads BM..BM+BN-1 stage im2col(x): both are the same gather with different (wave-uniform) parameters.
 // Split over pixel ranges (grid.y) into the caller's workspace + splitk_reduce, as the fp32 kernel.
-#include "wgrad_common.hpp"
-#include "x3_common.hpp"
+#include "wgrad_tile.hpp"
 #include <stdlib.h>
 
 namespace evk {
@@ -35,17 +34,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WGradArgs p) {
   unsigned char* const Ap = smem3;                      // [3][BM][64 B]
   unsigned char* const Bp = smem3 + 3 * BM * kRowBytes;  // [3][BN][64 B]
 
-  // XCD-aware order: all (co, k) tiles of one pixel chunk z run on the same XCD, so the chunk's dy / x
-  // rows are fetched into ONE L2 instead of eight (PMC: 3.4x the algorithmic bytes with the default order)
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int ntile = p.tiles_co * p.tiles_k;
-  const int z = bid / ntile;
-  const int tile = bid - z * ntile;
-  const int tile_k = tile % p.tiles_k;
-  const int tile_co = tile / p.tiles_k;
-  const int co0 = tile_co * BM, k0 = tile_k * BN;
-  const int pbeg = z * p.chunk;
-  const int pend = min(p.M, pbeg + p.chunk);
+  const WGradTile tl(p, BM, BN);
+  const int z = tl.z, co0 = tl.co0, k0 = tl.k0, pbeg = tl.pbeg;
+  WGRAD_PIXEL_RANGE(p, pbeg);
 
   const int tid = threadIdx.x;
   // ---- staging role (wave-uniform): which tensor this thread gathers, and how
@@ -55,24 +46,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WGradArgs p) {
   const int Q = roleA ? QA : QB;
   const int cq = idx % Q;  // channel quad
   const int pg = idx / Q;  // pixel group (8 pixels) 0..3
-  const float* const src = roleA ? p.dy : p.x;
-  const int Hs = roleA ? p.Ho : p.H, Ws = roleA ? p.Wo : p.W, Cs = roleA ? p.Cout : p.Cin;
-  const int ssh = roleA ? 1 : p.sh, ssw = roleA ? 1 : p.sw;
-  int offy = 0, offx = 0, coff = 0;
-  bool cvalid = false;
+  const PtrLoad ld(roleA ? p.dy : p.x);
+  WGather g{roleA ? p.Ho : p.H, roleA ? p.Wo : p.W, roleA ? p.Cout : p.Cin, roleA ? 1 : p.sh, roleA ? 1 : p.sw, 0, 0, 0, false};
   if (roleA) {
-    coff = co0 + cq * 4;
-    cvalid = coff < p.Cout;
+    g.coff = co0 + cq * 4;
+    g.cvalid = g.coff < p.Cout;
   } else if (staged) {
-    const int q = (k0 >> 2) + cq;
-    cvalid = q * 4 < p.Ktot;
-    if (cvalid) {
-      const int tap = q / p.cpt;
-      coff = (q - tap * p.cpt) * 4;
-      const int ky = tap / p.kw, kx = tap - ky * p.kw;
-      offy = ky * p.dh - p.ph;
-      offx = kx * p.dw - p.pw;
-    }
+    const WGradTap tap(p, (k0 >> 2) + cq);
+    g.offy = tap.offy; g.offx = tap.offx; g.coff = tap.coff;
+    g.cvalid = tap.valid;
   }
   unsigned char* const st_base = (roleA ? Ap : Bp);
   const int st_plane = (roleA ? BM : BN) * kRowBytes;
@@ -88,69 +70,16 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WGradArgs p) {
   const bool st_packed = PK && (roleA ? p.dy_packed : p.x_packed) != 0;   // wave-uniform
 
   auto load_tiles = [&](int pix0) {
-    okmask = 0;
-    const int m0 = pix0 + pg * 8;
-    if ((p.Wo & 7) == 0) {
-      // the 8 pixels share an output row: one (n, oy, ox) decomposition per micro-block
-      const uint32_t mm = (uint32_t)min(m0, p.M - 1);
-      const uint32_t n = fdiv(mm, p.fd_hw);
-      const uint32_t rem = mm - n * p.fd_hw.div;
-      const uint32_t oy = fdiv(rem, p.fd_w);
-      const int ox = (int)(rem - oy * p.fd_w.div);
-      const int sy = (int)oy * ssh + offy;
-      const bool rowok = cvalid && m0 < pend && (unsigned)sy < (unsigned)Hs;
-      const int base = ((int)n * Hs + sy) * Ws * Cs + coff;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int sx = (ox + j) * ssw + offx;
-        const bool ok = rowok && (unsigned)sx < (unsigned)Ws;
-        okmask |= ok ? (1u << j) : 0u;
-        rv[j] = *reinterpret_cast<const f32x4*>(src + (ok ? base + sx * Cs : 0));
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int m = m0 + j;
-        const uint32_t mm = (uint32_t)min(m, p.M - 1);
-        const uint32_t n = fdiv(mm, p.fd_hw);
-        const uint32_t rem = mm - n * p.fd_hw.div;
-        const uint32_t oy = fdiv(rem, p.fd_w);
-        const int ox = (int)(rem - oy * p.fd_w.div);
-        const int sy = (int)oy * ssh + offy, sx = ox * ssw + offx;
-        const bool ok = cvalid && m < pend && (unsigned)sy < (unsigned)Hs && (unsigned)sx < (unsigned)Ws;
-        okmask |= ok ? (1u << j) : 0u;
-        rv[j] = *reinterpret_cast<const f32x4*>(src + (ok ? (((int)n * Hs + sy) * Ws + sx) * Cs + coff : 0));
-      }
-    }
+    // (Wo % 8 == 0: the 8 pixels share an output row, one (n, oy, ox) decomposition per micro-block)
+    if ((p.Wo & 7) == 0) gather8<true>(p, g, ld, pix0 + pg * 8, pend, rv, okmask);
+    else gather8<false>(p, g, ld, pix0 + pg * 8, pend, rv, okmask);
   };
-
   auto store_tiles = [&]() {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const bool ok = (okmask >> j) & 1u;
-      rv[j].x = ok ? rv[j].x : 0.f; rv[j].y = ok ? rv[j].y : 0.f;
-      rv[j].z = ok ? rv[j].z : 0.f; rv[j].w = ok ? rv[j].w : 0.f;
+    zero_masked(rv, okmask);
+    if constexpr (PK) {
+      if (st_packed) return split_store<NP, 4, true>(rv, st_base, st_plane, Q, cq, pg, st_inv);
     }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int row = e * Q + cq;
-      const int off = wg_off(row, pg);
-      u32x4 H, M, L;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        uint32_t h, m = 0, l = 0;
-        if constexpr (PK) {
-          if (st_packed) split_op<NP, true>(rv[2 * t][e], rv[2 * t + 1][e], st_inv, h, m, l);
-          else split_np<NP>(rv[2 * t][e], rv[2 * t + 1][e], st_inv, h, m, l);
-        } else {
-          split_np<NP>(rv[2 * t][e], rv[2 * t + 1][e], st_inv, h, m, l);
-        }
-        H[t] = h; M[t] = m; L[t] = l;
-      }
-      *reinterpret_cast<u32x4*>(st_base + off) = H;
-      if (NP >= 2) *reinterpret_cast<u32x4*>(st_base + st_plane + off) = M;
-      if (NP == 3) *reinterpret_cast<u32x4*>(st_base + 2 * st_plane + off) = L;
-    }
+    split_store<NP, 4, false>(rv, st_base, st_plane, Q, cq, pg, st_inv);
   };
 
   const int wave = tid >> 6, lane = tid & 63;
@@ -167,36 +96,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WGradArgs p) {
 
   int fa_off[MB][2], fb_off[NB][2];
 #pragma unroll
-  for (int a = 0; a < MB; ++a)
+  for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) fa_off[a][kk] = wg_off(wm * WM + a * 32 + li, 2 * kk + lh);
+    for (int a = 0; a < MB; ++a) fa_off[a][kk] = wg_off(wm * WM + a * 32 + li, 2 * kk + lh);
 #pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) fb_off[b][kk] = wg_off(wn * WN + b * 32 + li, 2 * kk + lh);
+    for (int b = 0; b < NB; ++b) fb_off[b][kk] = wg_off(wn * WN + b * 32 + li, 2 * kk + lh);
+  }
 
-  auto half_step = [&](int kk) {
-    bf16x8 fa[MB][3], fb[NB][3];
-#pragma unroll
-    for (int a = 0; a < MB; ++a)
-#pragma unroll
-      for (int pt = 0; pt < NP; ++pt)
-        fa[a][pt] = *reinterpret_cast<const bf16x8*>(Ap + pt * BM * kRowBytes + fa_off[a][kk]);
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int pt = 0; pt < NP; ++pt)
-        fb[b][pt] = *reinterpret_cast<const bf16x8*>(Bp + pt * BN * kRowBytes + fb_off[b][kk]);
-#pragma unroll
-    for (int t = 0; t < X3Prod<NP>::N; ++t)
-#pragma unroll
-      for (int a = 0; a < MB; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-          acc[a][b] = mfma_np<NP>(fa[a][x3_pa(NP, t)], fb[b][x3_pb(NP, t)], acc[a][b]);
-  };
-
-  const int nk = (pend - pbeg + BKP - 1) / BKP;
   if (nk > 0 && staged) {
     load_tiles(pbeg);
     store_tiles();
@@ -206,8 +112,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WGradArgs p) {
   for (int kt = 0; kt < nk; ++kt) {
     const bool more = kt + 1 < nk;
     if (more && staged) load_tiles(pbeg + (kt + 1) * BKP);
-    half_step(0);
-    half_step(1);
+    half_step<MB, NB, NP>(acc, Ap, Bp, BM * kRowBytes, BN * kRowBytes, fa_off, fb_off, 0);
+    half_step<MB, NB, NP>(acc, Ap, Bp, BM * kRowBytes, BN * kRowBytes, fa_off, fb_off, 1);
     __syncthreads();
     if (more) {
       if (staged) store_tiles();
@@ -233,31 +139,16 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WGradArgs p) {
     }
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N>
-static int launch_one(const WGradArgs& a, int npx, hipStream_t stream) {
-  const size_t lds = (size_t)3 * (BM + BN) * kRowBytes;
-  if (npx == 1) {
-    hipLaunchKernelGGL((conv_wgrad_x3_kernel<BM, BN, WAVES_M, WAVES_N, 1>), dim3(a.tiles_co * a.tiles_k * a.splitk),
-                       dim3(256), lds, stream, a);
-  } else if (npx == 4) {
-    hipLaunchKernelGGL((conv_wgrad_x3_kernel<BM, BN, WAVES_M, WAVES_N, 4>), dim3(a.tiles_co * a.tiles_k * a.splitk),
-                       dim3(256), lds, stream, a);
-  } else if (npx == 2) {
-    hipLaunchKernelGGL((conv_wgrad_x3_kernel<BM, BN, WAVES_M, WAVES_N, 2>), dim3(a.tiles_co * a.tiles_k * a.splitk),
-                       dim3(256), lds, stream, a);
-  } else {
-    hipLaunchKernelGGL((conv_wgrad_x3_kernel<BM, BN, WAVES_M, WAVES_N, 3>), dim3(a.tiles_co * a.tiles_k * a.splitk),
-                       dim3(256), lds, stream, a);
-  }
-  return check_launch("conv_wgrad_x3");
-}
-
 int launch_wgrad_x3(const WGradArgs& a, const WGradRoute& r, hipStream_t stream) {
   if (r.kernel == WGradKernel::X3Ws) return launch_wgrad_x3ws(a, r, stream);
-  if (r.plan.bm == 128 && r.plan.bn == 128) return launch_one<128, 128, 2, 2>(a, r.npx, stream);
-  if (r.plan.bm == 64 && r.plan.bn == 128) return launch_one<64, 128, 2, 2>(a, r.npx, stream);
-  if (r.plan.bm == 128 && r.plan.bn == 64) return launch_one<128, 64, 2, 2>(a, r.npx, stream);
-  return launch_one<64, 64, 2, 2>(a, r.npx, stream);
+  return pick_tile(r.plan.bm, r.plan.bn, [&](auto BM, auto BN) {
+    return pick<1, 4, 2, 3>(r.npx, [&](auto NPX) {
+      constexpr int bm = decltype(BM)::value, bn = decltype(BN)::value;
+      hipLaunchKernelGGL((conv_wgrad_x3_kernel<bm, bn, 2, 2, decltype(NPX)::value>), dim3(a.tiles_co * a.tiles_k * a.splitk),
+                         dim3(256), (size_t)3 * (bm + bn) * kRowBytes, stream, a);
+      return check_launch("conv_wgrad_x3");
+    });
+  });
 }
 
 }  // namespace evk

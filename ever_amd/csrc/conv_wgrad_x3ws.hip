@@ -7,212 +7,10 @@
 //              the register transpose into the pixel-contiguous planes; two register sets deep, two LDS stages.
 // Against the 128x128 single-role kernel: 25 % fewer operand elements (loads and splits) per MFMA, and the
 // split no longer shares a wave with the MFMA stream.
-#include "wgrad_common.hpp"
-#include "x3_common.hpp"
+#include "wgrad_tile.hpp"
 #include <stdlib.h>
-#include <type_traits>
 
-#ifndef EVK_WG_ABL
-#define EVK_WG_ABL 0   // timing ablations (tools/build_variant.sh -DEVK_WG_ABL=n; wrong results): 1 no loads, 2 no split / LDS writes,
-#endif                 // 4 no fragment reads / MFMAs, 8 no stores
 namespace evk {
-constexpr int kWgAbl = EVK_WG_ABL;
-
-
-struct WGather {
-  const float* src;
-  int Hs, Ws, Cs, ssh, ssw, offy, offx, coff;
-  bool cvalid;
-};
-
-// W8: Wo % 8 == 0 (every map of this network): the 8 pixels of a micro-block lie in one image row, one decomposition
-// (two fast divisions) per micro-block, running sums for the column and the address.  The instantiation carries no
-// code of the per-pixel path — the staging waves are VALU-issue bound (PMC: 83 % VALU-busy with the matrix waves idle).
-template <bool W8>
-__device__ __forceinline__ void gather8(const WGradArgs& p, const WGather& g, int m0, int pend, f32x4 (&rv)[8],
-                                        uint32_t& okmask) {
-  okmask = 0;
-  if (W8) {
-    const uint32_t mm = (uint32_t)min(m0, p.M - 1);
-    const uint32_t n = fdiv(mm, p.fd_hw);
-    const uint32_t rem = mm - n * p.fd_hw.div;
-    const uint32_t oy = fdiv(rem, p.fd_w);
-    const int ox = (int)(rem - oy * p.fd_w.div);
-    const int sy = (int)oy * g.ssh + g.offy;
-    const bool rowok = g.cvalid && m0 < pend && (unsigned)sy < (unsigned)g.Hs;
-    int sx = ox * g.ssw + g.offx;
-    int off = (((int)n * g.Hs + sy) * g.Ws + sx) * g.Cs + g.coff;
-    const int dsx = g.ssw, doff = g.ssw * g.Cs;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const bool ok = rowok && (unsigned)sx < (unsigned)g.Ws;
-      okmask |= ok ? (1u << j) : 0u;
-      rv[j] = *reinterpret_cast<const f32x4*>(g.src + (ok ? off : 0));
-      sx += dsx;
-      off += doff;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int m = m0 + j;
-      const uint32_t mm = (uint32_t)min(m, p.M - 1);
-      const uint32_t n = fdiv(mm, p.fd_hw);
-      const uint32_t rem = mm - n * p.fd_hw.div;
-      const uint32_t oy = fdiv(rem, p.fd_w);
-      const int ox = (int)(rem - oy * p.fd_w.div);
-      const int sy = (int)oy * g.ssh + g.offy, sx = ox * g.ssw + g.offx;
-      const bool ok = g.cvalid && m < pend && (unsigned)sy < (unsigned)g.Hs && (unsigned)sx < (unsigned)g.Ws;
-      okmask |= ok ? (1u << j) : 0u;
-      rv[j] = *reinterpret_cast<const f32x4*>(g.src + (ok ? (((int)n * g.Hs + sy) * g.Ws + sx) * g.Cs + g.coff : 0));
-    }
-  }
-}
-
-// split the micro-block and write channel 4*cq+e to LDS row e*Q + cq, 16-byte chunk pg, of the three planes
-template <int NP>
-__device__ __forceinline__ void split_store8(f32x4 (&rv)[8], uint32_t okmask, unsigned char* base, int plane_bytes, int Q,
-                                             int cq, int pg, float inv) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const bool ok = (okmask >> j) & 1u;
-    rv[j].x = ok ? rv[j].x : 0.f; rv[j].y = ok ? rv[j].y : 0.f;
-    rv[j].z = ok ? rv[j].z : 0.f; rv[j].w = ok ? rv[j].w : 0.f;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int off = wg_off(e * Q + cq, pg);
-    u32x4 H, M, L;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uint32_t h, m = 0, l = 0;
-      split_np<NP>(rv[2 * t][e], rv[2 * t + 1][e], inv, h, m, l);
-      H[t] = h; M[t] = m; L[t] = l;
-    }
-    *reinterpret_cast<u32x4*>(base + off) = H;
-    if (NP >= 2) *reinterpret_cast<u32x4*>(base + plane_bytes + off) = M;
-    if (NP == 3) *reinterpret_cast<u32x4*>(base + 2 * plane_bytes + off) = L;
-  }
-}
-
-// Half micro-block of dy: 8 pixels x 2 channels (8-byte loads, 512 B contiguous per pixel across a wave).  dy is the
-// plain [M][Cout] matrix: no tap, no spatial bound, only the pixel range.  Channel 2*cq+e goes to LDS row e*Q2 + cq.
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void gather8h(const float* __restrict__ dy, int Cout, int coff, bool cvalid, int m0, int pend,
-                                         f32x2v (&rv)[8], uint32_t& okmask) {
-  okmask = 0;
-  int off = m0 * Cout + coff;      // (both tensors are below 2^31 bytes: plan_wgrad's fits32)
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const bool ok = cvalid && m0 + j < pend;
-    okmask |= ok ? (1u << j) : 0u;
-    rv[j] = *reinterpret_cast<const f32x2v*>(dy + (ok ? off : 0));
-    off += Cout;
-  }
-}
-// ---- buffer-load gathers (the f16x2 instantiation, where they measure faster: staging alone 874 -> 771 us, whole
-// kernel 1326 -> 1301 / 320 -> 277 / 90 -> 80 us on 3x3x256 @128^2 / 64^2 / 32^2; under bf16x3 they are slower, 1567 ->
-// 1726): 32-bit byte offsets on a buffer resource, out-of-image pixels get an
-// out-of-range offset and the hardware returns zeros — no 64-bit address arithmetic, no selects on the loaded data.
-// The pixel decomposition (two fast divisions) is done once per micro-block when Wo % 8 == 0 (always the case for the
-// maps of this network); the generic path decomposes every pixel.
-constexpr uint32_t kOOBOff = 0x80000000u;
-typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 bload16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ f32x2v bload8(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  return __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0));
-}
-template <bool W8>
-__device__ __forceinline__ void gather8_buf(const WGradArgs& p, const WGather& g, __amdgpu_buffer_rsrc_t rs, int m0, int pend,
-                                            f32x4 (&rv)[8]) {
-  if (W8) {
-    const uint32_t mm = (uint32_t)min(m0, p.M - 1);
-    const uint32_t n = fdiv(mm, p.fd_hw);
-    const uint32_t rem = mm - n * p.fd_hw.div;
-    const uint32_t oy = fdiv(rem, p.fd_w);
-    const int ox = (int)(rem - oy * p.fd_w.div);
-    const int sy = (int)oy * g.ssh + g.offy;
-    const bool rowok = g.cvalid && m0 < pend && (unsigned)sy < (unsigned)g.Hs;
-    int sx = ox * g.ssw + g.offx;
-    const uint32_t step = (uint32_t)(g.ssw * g.Cs) << 2;
-    uint32_t off = (uint32_t)((((int)n * g.Hs + sy) * g.Ws + sx) * g.Cs + g.coff) << 2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const bool ok = rowok && (unsigned)sx < (unsigned)g.Ws;
-      rv[j] = bload16(rs, ok ? off : kOOBOff);
-      sx += g.ssw;
-      off += step;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int m = m0 + j;
-      const uint32_t mm = (uint32_t)min(m, p.M - 1);
-      const uint32_t n = fdiv(mm, p.fd_hw);
-      const uint32_t rem = mm - n * p.fd_hw.div;
-      const uint32_t oy = fdiv(rem, p.fd_w);
-      const int ox = (int)(rem - oy * p.fd_w.div);
-      const int sy = (int)oy * g.ssh + g.offy, sx = ox * g.ssw + g.offx;
-      const bool ok = g.cvalid && m < pend && (unsigned)sy < (unsigned)g.Hs && (unsigned)sx < (unsigned)g.Ws;
-      rv[j] = bload16(rs, ok ? (uint32_t)((((int)n * g.Hs + sy) * g.Ws + sx) * g.Cs + g.coff) << 2 : kOOBOff);
-    }
-  }
-}
-__device__ __forceinline__ void gather8h_buf(__amdgpu_buffer_rsrc_t rs, int Cout, int coff, bool cvalid, int m0, int pend,
-                                             f32x2v (&rv)[8]) {
-  uint32_t off = (uint32_t)(m0 * Cout + coff) << 2;
-  const uint32_t step = (uint32_t)Cout << 2;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    rv[j] = bload8(rs, (cvalid && m0 + j < pend) ? off : kOOBOff);
-    off += step;
-  }
-}
-// split the micro-block (already zero where out of range) and write channel 4*cq+e to LDS row e*Q + cq, chunk pg
-template <int NP, int NCH, bool PK, typename V>
-__device__ __forceinline__ void split_store_buf(V (&rv)[8], unsigned char* base, int plane_bytes, int Q, int cq, int pg,
-                                                float inv) {
-#pragma unroll
-  for (int e = 0; e < NCH; ++e) {
-    const int off = wg_off(e * Q + cq, pg);
-    u32x4 H, M, L;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uint32_t h, m = 0, l = 0;
-      split_op<NP, PK>(rv[2 * t][e], rv[2 * t + 1][e], inv, h, m, l);
-      H[t] = h; M[t] = m; L[t] = l;
-    }
-    *reinterpret_cast<u32x4*>(base + off) = H;
-    if (NP >= 2) *reinterpret_cast<u32x4*>(base + plane_bytes + off) = M;
-    if (NP == 3) *reinterpret_cast<u32x4*>(base + 2 * plane_bytes + off) = L;
-  }
-}
-
-template <int NP>
-__device__ __forceinline__ void split_store8h(f32x2v (&rv)[8], uint32_t okmask, unsigned char* base, int plane_bytes, int Q2,
-                                              int cq, int pg, float inv) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const bool ok = (okmask >> j) & 1u;
-    rv[j].x = ok ? rv[j].x : 0.f;
-    rv[j].y = ok ? rv[j].y : 0.f;
-  }
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int off = wg_off(e * Q2 + cq, pg);
-    u32x4 H, M, L;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uint32_t h, m = 0, l = 0;
-      split_np<NP>(rv[2 * t][e], rv[2 * t + 1][e], inv, h, m, l);
-      H[t] = h; M[t] = m; L[t] = l;
-    }
-    *reinterpret_cast<u32x4*>(base + off) = H;
-    if (NP >= 2) *reinterpret_cast<u32x4*>(base + plane_bytes + off) = M;
-    if (NP == 3) *reinterpret_cast<u32x4*>(base + 2 * plane_bytes + off) = L;
-  }
-}
 
 // PKX / PKD: x / dy arrive packed (f16x2 only; x3_common.hpp)
 template <int BM, int BN, int NP, bool W8, bool PKX = false, bool PKD = false>
@@ -226,16 +24,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_x3ws_kernel(const WGradArgs p)
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem3[];
 
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int ntile = p.tiles_co * p.tiles_k;
-  const int z = bid / ntile;
-  const int tile = bid - z * ntile;
-  const int tile_k = tile % p.tiles_k;
-  const int tile_co = tile / p.tiles_k;
-  const int co0 = tile_co * BM, k0 = tile_k * BN;
-  const int pbeg = z * p.chunk;
-  const int pend = min(p.M, pbeg + p.chunk);
-  const int nk = (pend - pbeg + BKP - 1) / BKP;
+  const WGradTile tl(p, BM, BN);
+  const int z = tl.z, co0 = tl.co0, k0 = tl.k0, pbeg = tl.pbeg;
+  WGRAD_PIXEL_RANGE(p, pbeg);
   const int tid = threadIdx.x;
 
   if (tid >= 256) {
@@ -246,30 +37,18 @@ __global__ __launch_bounds__(512) void conv_wgrad_x3ws_kernel(const WGradArgs p)
     // measured 51 % matrix-pipe occupancy, the matrix waves waiting at the barrier)
     constexpr int QA2 = BM / 2;
     static_assert(QA2 * 4 == 256, "one half dy micro-block per staging thread");
-    WGather gb;
     const int bcq = ptid % QB, bpg = ptid / QB;
     const int acq = ptid % QA2, apg = ptid / QA2;
     const int a_coff = co0 + acq * 2;
     const bool a_cvalid = a_coff < p.Cout;
-    {
-      gb.src = p.x; gb.Hs = p.H; gb.Ws = p.W; gb.Cs = p.Cin; gb.ssh = p.sh; gb.ssw = p.sw;
-      const int q = (k0 >> 2) + bcq;
-      gb.cvalid = q * 4 < p.Ktot;
-      gb.offy = gb.offx = gb.coff = 0;
-      if (gb.cvalid) {
-        const int tap = q / p.cpt;
-        gb.coff = (q - tap * p.cpt) * 4;
-        const int ky = tap / p.kw, kx = tap - ky * p.kw;
-        gb.offy = ky * p.dh - p.ph;
-        gb.offx = kx * p.dw - p.pw;
-      }
-    }
+    const WGradTap tap(p, (k0 >> 2) + bcq);
+    const WGather gb{p.H, p.W, p.Cin, p.sh, p.sw, tap.offy, tap.offx, tap.coff, tap.valid};
     f32x2v ra[2][8];
     f32x4 rb[2][8];
     uint32_t oka[2] = {0, 0}, okb[2] = {0, 0};
-    constexpr bool kBuf = NP == 2;   // buffer loads with out-of-range zero fill
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.N * p.H * p.W * p.Cin * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.M * p.Cout * 4, 0x00020000);
+    // f16x2: buffer loads with out-of-range zero fill (the other arithmetics measure slower with them: wgrad_tile.hpp)
+    using Ld = std::conditional_t<NP == 2, BufLoad, PtrLoad>;
+    const Ld ld_x(p.x, p.N * p.H * p.W * p.Cin * 4), ld_dy(p.dy, p.M * p.Cout * 4);
     float x_inv = 1.f, dy_inv = 1.f;   // f16x2: 1 / operand scales
     if constexpr (NP == 2) {
       x_inv = op_scale(act_absmax(p.x_scale)).inv;
@@ -280,26 +59,20 @@ __global__ __launch_bounds__(512) void conv_wgrad_x3ws_kernel(const WGradArgs p)
       constexpr int s = decltype(SET)::value;
       const int pix0 = pbeg + kt * BKP;
       if (kWgAbl & 1) return;   // ablation: no global loads
-      if constexpr (kBuf) {
-        gather8_buf<W8>(p, gb, rs_x, pix0 + bpg * 8, pend, rb[s]);
-        gather8h_buf(rs_dy, p.Cout, a_coff, a_cvalid, pix0 + apg * 8, pend, ra[s]);
-      } else {
-        gather8<W8>(p, gb, pix0 + bpg * 8, pend, rb[s], okb[s]);
-        gather8h(p.dy, p.Cout, a_coff, a_cvalid, pix0 + apg * 8, pend, ra[s], oka[s]);
-      }
+      gather8<W8>(p, gb, ld_x, pix0 + bpg * 8, pend, rb[s], okb[s]);
+      gather8h(ld_dy, p.Cout, a_coff, a_cvalid, pix0 + apg * 8, pend, ra[s], oka[s]);
     };
     auto store = [&](auto SET, int stage) {
       constexpr int s = decltype(SET)::value;
       unsigned char* Ab = smem3 + stage * kStage;
       unsigned char* Bb = Ab + 3 * BM * kRowBytes;
       if (kWgAbl & 2) return;   // ablation: no split, no LDS writes
-      if constexpr (kBuf) {
-        split_store_buf<NP, 4, PKX>(rb[s], Bb, BN * kRowBytes, QB, bcq, bpg, x_inv);
-        split_store_buf<NP, 2, PKD>(ra[s], Ab, BM * kRowBytes, QA2, acq, apg, dy_inv);
-      } else {
-        split_store8<NP>(rb[s], okb[s], Bb, BN * kRowBytes, QB, bcq, bpg, x_inv);
-        split_store8h<NP>(ra[s], oka[s], Ab, BM * kRowBytes, QA2, acq, apg, dy_inv);
+      if constexpr (!Ld::kZeroFill) {
+        zero_masked(rb[s], okb[s]);
+        zero_masked(ra[s], oka[s]);
       }
+      split_store<NP, 4, PKX>(rb[s], Bb, BN * kRowBytes, QB, bcq, bpg, x_inv);
+      split_store<NP, 2, PKD>(ra[s], Ab, BM * kRowBytes, QA2, acq, apg, dy_inv);
     };
     using S0 = std::integral_constant<int, 0>;
     using S1 = std::integral_constant<int, 1>;
@@ -341,6 +114,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_x3ws_kernel(const WGradArgs p)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
+  // im2col LDS row e * QB + q holds channel 4q + e of the k range (staging permutation).  Matrix wave wn takes q in
+  // [32 wn, 32 wn + 32) of ALL four e-blocks as its NB = 4 column blocks: lane li then owns the four CONSECUTIVE
+  // k columns 4 (32 wn + li) + {0..3} across its blocks, i.e. one 16-byte store per accumulator row.
   int fa_off[MB][2], fb_off[NB][2];
 #pragma unroll
   for (int a = 0; a < MB; ++a)
@@ -349,38 +125,14 @@ __global__ __launch_bounds__(512) void conv_wgrad_x3ws_kernel(const WGradArgs p)
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
-    // im2col LDS row e * QB + q holds channel 4q + e of the k range (staging permutation).  Matrix wave wn takes q in
-    // [32 wn, 32 wn + 32) of ALL four e-blocks as its NB = 4 column blocks: lane li then owns the four CONSECUTIVE
-    // k columns 4 (32 wn + li) + {0..3} across its blocks, i.e. one 16-byte store per accumulator row.
     for (int kk = 0; kk < 2; ++kk) fb_off[b][kk] = 3 * BM * kRowBytes + wg_off(b * QB + wn * 32 + li, 2 * kk + lh);
-
-  auto half_step = [&](const unsigned char* S, int kk) {
-    bf16x8 fa[MB][3], fb[NB][3];
-#pragma unroll
-    for (int a = 0; a < MB; ++a)
-#pragma unroll
-      for (int pt = 0; pt < NP; ++pt)
-        fa[a][pt] = *reinterpret_cast<const bf16x8*>(S + pt * BM * kRowBytes + fa_off[a][kk]);
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int pt = 0; pt < NP; ++pt)
-        fb[b][pt] = *reinterpret_cast<const bf16x8*>(S + pt * BN * kRowBytes + fb_off[b][kk]);
-#pragma unroll
-    for (int t = 0; t < X3Prod<NP>::N; ++t)
-#pragma unroll
-      for (int a = 0; a < MB; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-          acc[a][b] = mfma_np<NP>(fa[a][x3_pa(NP, t)], fb[b][x3_pb(NP, t)], acc[a][b]);
-  };
 
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     const unsigned char* S = smem3 + (kt & 1) * kStage;
     if (!(kWgAbl & 4)) {      // ablation: no fragment reads / MFMAs
-      half_step(S, 0);
-      half_step(S, 1);
+      half_step<MB, NB, NP>(acc, S, S, BM * kRowBytes, BN * kRowBytes, fa_off, fb_off, 0);
+      half_step<MB, NB, NP>(acc, S, S, BM * kRowBytes, BN * kRowBytes, fa_off, fb_off, 1);
     }
     __syncthreads();
   }
@@ -418,7 +170,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_x3ws_kernel(const WGradArgs p)
 }
 
 template <int NP, bool W8, bool PKX = false, bool PKD = false>
-static int launch_wgrad_x3ws_t(const WGradArgs& b, hipStream_t stream) {
+static int launch_wgrad_x3ws_t(const WGradArgs& a, hipStream_t stream) {
   constexpr int BM = 128, BN = 256;
   const size_t lds = (size_t)2 * 3 * (BM + BN) * kRowBytes;
   static PerDeviceOnce attr_once;
@@ -426,22 +178,23 @@ static int launch_wgrad_x3ws_t(const WGradArgs& b, hipStream_t stream) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_x3ws_kernel<BM, BN, NP, W8, PKX, PKD>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
-  hipLaunchKernelGGL((conv_wgrad_x3ws_kernel<BM, BN, NP, W8, PKX, PKD>), dim3(b.tiles_co * b.tiles_k * b.splitk), dim3(512), lds, stream, b);
+  hipLaunchKernelGGL((conv_wgrad_x3ws_kernel<BM, BN, NP, W8, PKX, PKD>), dim3(a.tiles_co * a.tiles_k * a.splitk), dim3(512), lds, stream, a);
   return check_launch("conv_wgrad_x3ws");
 }
 
 int launch_wgrad_x3ws(const WGradArgs& a, const WGradRoute& r, hipStream_t stream) {
-  WGradArgs b = a;
-  const bool w8 = r.w8 != 0;
-  if (r.npx == 1) return w8 ? launch_wgrad_x3ws_t<1, true>(b, stream) : launch_wgrad_x3ws_t<1, false>(b, stream);
-  if (r.npx == 2) {
-    const int pk = (r.pkx ? 1 : 0) | (r.pkd ? 2 : 0);
-    if (pk == 3) return w8 ? launch_wgrad_x3ws_t<2, true, true, true>(b, stream) : launch_wgrad_x3ws_t<2, false, true, true>(b, stream);
-    if (pk == 2) return w8 ? launch_wgrad_x3ws_t<2, true, false, true>(b, stream) : launch_wgrad_x3ws_t<2, false, false, true>(b, stream);
-    if (pk == 1) return w8 ? launch_wgrad_x3ws_t<2, true, true, false>(b, stream) : launch_wgrad_x3ws_t<2, false, true, false>(b, stream);
-    return w8 ? launch_wgrad_x3ws_t<2, true>(b, stream) : launch_wgrad_x3ws_t<2, false>(b, stream);
-  }
-  return w8 ? launch_wgrad_x3ws_t<3, true>(b, stream) : launch_wgrad_x3ws_t<3, false>(b, stream);
+  return pick<1, 2, 3>(r.npx, [&](auto NP) {
+    return pick<1, 0>(r.w8, [&](auto W8) {
+      constexpr int np = decltype(NP)::value;
+      constexpr bool w8 = decltype(W8)::value != 0;
+      if constexpr (np != 2) return launch_wgrad_x3ws_t<np, w8>(a, stream);   // (packed operands: f16x2 only)
+      else return pick<1, 0>(r.pkx, [&](auto PKX) {
+        return pick<1, 0>(r.pkd, [&](auto PKD) {
+          return launch_wgrad_x3ws_t<np, w8, decltype(PKX)::value != 0, decltype(PKD)::value != 0>(a, stream);
+        });
+      });
+    });
+  });
 }
 
 }  // namespace evk

@@ -1,6 +1,7 @@
-// Shared pieces of the weight-gradient kernels (fp32 MFMA and 3-way-bf16-split MFMA).
+// Host side of the weight-gradient family: arguments, plan, route and the launchers' prototypes (device pieces: wgrad_tile.hpp).
 #pragma once
 #include "common.hpp"
+#include <type_traits>
 
 namespace evk {
 
@@ -49,10 +50,31 @@ struct WGradRoute {
 // EVK_OK, or the error (with evk_last_error set) the launch entry points report for the same descriptor and flags.
 int route_wgrad(const evk_conv_desc* d, int planes, uint32_t flags, WGradRoute* r);
 void wgrad_kernel_name(const WGradRoute& r, char* buf, size_t n);
+int launch_wgrad_f32(const WGradArgs& a, const WGradRoute& r, hipStream_t stream);
 int launch_wgrad_x3(const WGradArgs& a, const WGradRoute& r, hipStream_t stream);
 int launch_wgrad_x3ws(const WGradArgs& a, const WGradRoute& r, hipStream_t stream);
 bool wgrad_tr_applicable(const evk_conv_desc* d, int planes);
 bool wgrad_tr_nine_tap(const evk_conv_desc* d);
 int launch_wgrad_tr(const WGradArgs& a, const WGradRoute& r, hipStream_t stream);
+
+// every flag evk_conv2d_wgrad_f16x2_ex and evk_conv2d_wgrad_route know
+constexpr uint32_t kWGradFlags = EVK_CONV_X_PACKED | EVK_CONV_DY_PACKED | EVK_CONV_X_PLANAR | EVK_CONV_DY_PLANAR | EVK_CONV_WGRAD_SHARED;
+
+// column sums of a [rows][c] fp32 matrix (bias gradients; conv_wgrad.hip): also used by conv_transpose.hip
+size_t colsum_workspace_bytes(int64_t rows, int c);
+int launch_colsum(const float* src, float* out, int64_t rows, int c, float* workspace, hipStream_t st);
+
+// Run-time value -> template argument: f(std::integral_constant<int, V>{}) for the listed V that equals v, the LAST one when
+// none does.
+template <int V0, int... Vs, typename F>
+inline int pick(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+  else return v == V0 ? f(std::integral_constant<int, V0>{}) : pick<Vs...>(v, f);
+}
+// the (bm, bn) tiles of the single-role kernels: f(BM, BN)
+template <typename F>
+inline int pick_tile(int bm, int bn, F&& f) {
+  return pick<128, 64>(bm, [&](auto BM) { return pick<128, 64>(bn, [&](auto BN) { return f(BM, BN); }); });
+}
 
 }  // namespace evk
