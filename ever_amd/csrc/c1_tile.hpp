@@ -205,29 +205,13 @@ __device__ __forceinline__ void c1_last_step(uint32_t S, F& fx, F& fy, Read&& re
 inline unsigned long long c1_src_bytes(const IGemmArgs& a) { return (unsigned long long)a.N * a.Hs * a.Ws * a.Cs * 4ull; }
 inline unsigned long long c1_wgt_bytes(const IGemmArgs& a) { return 2ull * a.Cd * a.Kpad * 2ull; }
 
-// launch of a ring kernel (one workgroup per tile, `row_waves` x 2 compute waves, NST stages; the statistics epilogue
-// reuses the ring, so the LDS is the larger of the two).  A template on the kernel: the once-per-device attribute flag is
-// one per instantiation.  copies: workgroups per tile (2 under conv1x1_dma.hip's K-split timing probe)
+// launch of a ring kernel (`row_waves` x 2 compute waves, NST stages) through the family's tile launcher, with the two
+// buffer sizes as the kernel's extra arguments.  copies: workgroups per tile (2 under conv1x1_dma.hip's K-split timing probe)
 template <auto Kern, int BN, int NST>
 int launch_c1_ring(IGemmArgs& a, hipStream_t stream, int block, int row_waves, const char* name, int copies = 1) {
-  a.tiles_m = ceil_div(a.M, kC1BM);
-  a.tiles_n = ceil_div(a.Cd, BN);
-  bn_stats_setup(a, kC1BM, BN, row_waves, a.tiles_m);
-  size_t lds = (size_t)NST * C1Stage<BN>::bytes;
-  const size_t scratch = igemm_stats_scratch_bytes(row_waves, 2, BN / 2);
-  if (lds < scratch) lds = scratch;
-  static PerDeviceOnce attr_once;
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  const long long nwg = (long long)a.tiles_m * a.tiles_n;
-  if (nwg <= 0 || nwg > 0x7fffffffLL) {
-    set_error("%s: bad grid %lld", name, nwg);
-    return EVK_E_INVALID;
-  }
-  hipLaunchKernelGGL(Kern, dim3((unsigned)(copies * nwg)), dim3(block), lds, stream, a, (uint32_t)c1_src_bytes(a),
-                     (uint32_t)c1_wgt_bytes(a));
-  return check_launch(name);
+  return launch_igemm_tile<Kern>(a, stream, name, kC1BM, BN, row_waves, block, (size_t)NST * C1Stage<BN>::bytes,
+                                 igemm_stats_scratch_bytes(row_waves, 2, BN / 2), [&](long long tiles) { return copies * tiles; },
+                                 (uint32_t)c1_src_bytes(a), (uint32_t)c1_wgt_bytes(a));
 }
 
 }  // namespace evk

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <atomic>
+#include <type_traits>
 #include "../../include/ever_hip.h"
 
 namespace evk {
@@ -81,6 +82,19 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// Run-time value -> template argument: f(std::integral_constant<int, V>{}) for the listed V that equals v, the LAST one when
+// none does.
+template <int V0, int... Vs, typename F>
+inline int pick(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+  else return v == V0 ? f(std::integral_constant<int, V0>{}) : pick<Vs...>(v, f);
+}
+// the (bm, bn) tiles of the single-role kernels: f(BM, BN)
+template <typename F>
+inline int pick_tile(int bm, int bn, F&& f) {
+  return pick<128, 64>(bm, [&](auto BM) { return pick<128, 64>(bn, [&](auto BN) { return f(BM, BN); }); });
+}
 
 // ---- ReLU bits of an fp32 tensor: one bit per element ("the activation's output was positive"), written by the
 // BatchNorm + add + ReLU pass of a residual block and read wherever its backward needs the mask — 1/32 of the bytes of the

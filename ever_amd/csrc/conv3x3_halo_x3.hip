@@ -352,18 +352,14 @@ static int launch_halo_np(IGemmArgs& a, hipStream_t stream) {
   return check_launch("conv3x3_halo_x3");
 }
 
+// The f16x2 arithmetic takes its weight tiles by DMA (through registers as in the other arithmetics: 452.4 vs 465.0 tiles/s,
+// DESIGN 2.7), and the eight-matrix-wave form exists for it alone.
 template <int BN, int PH, int MW = 4>
 static int launch_halo(IGemmArgs& a, hipStream_t stream) {
-  if constexpr (MW == 8) {   // (the eight-matrix-wave form exists for the f16x2 arithmetic with DMA-fed weights)
-    if (a.planes == 2)
-      return a.a_packed ? launch_halo_np<BN, PH, 4, true, 8>(a, stream) : launch_halo_np<BN, PH, 2, true, 8>(a, stream);
-  }
-  if (a.planes == 1) return launch_halo_np<BN, PH, 1>(a, stream);
-  if (a.planes == 2) {
-    // (the weight tiles by DMA; through registers as in the other arithmetics: 452.4 vs 465.0 tiles/s)
-    return a.a_packed ? launch_halo_np<BN, PH, 4, true>(a, stream) : launch_halo_np<BN, PH, 2, true>(a, stream);
-  }
-  return launch_halo_np<BN, PH, 3>(a, stream);
+  return pick_npx(a, [&](auto NPX) {
+    constexpr bool F16 = X3Mode<decltype(NPX)::value>::NP == 2;
+    return launch_halo_np<BN, PH, decltype(NPX)::value, F16, F16 ? MW : 4>(a, stream);
+  });
 }
 
 int launch_conv3x3_halo(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {

@@ -12,9 +12,7 @@
 // LDS is a ring of NSTAGE stages; stage s of step kt is written while the matrix waves read step kt's
 // stage, one s_barrier per step for all 8 waves.
 #include "conv_route.hpp"
-#include "x3_common.hpp"
-#include <stdlib.h>
-#include <type_traits>
+#include "igemm_tile.hpp"
 
 namespace evk {
 
@@ -25,7 +23,8 @@ __global__ __launch_bounds__(512) void conv_igemm_x3ws_kernel(const IGemmArgs p)
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
   constexpr int MB = WM / 32, NB = WN / 32;
   constexpr int AR = BM / 64, BR = BN / 64;
-  constexpr int kStage = 3 * (BM + BN) * kRowBytes;
+  constexpr int kAPlane = BM * kRowBytes, kBPlane = BN * kRowBytes;
+  constexpr int kStage = 3 * (kAPlane + kBPlane);
   static_assert(WAVES_M * WAVES_N == 4, "4 matrix waves");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem3[];
@@ -48,46 +47,21 @@ __global__ __launch_bounds__(512) void conv_igemm_x3ws_kernel(const IGemmArgs p)
     const int c4 = ptid & 3;   // 8-float group inside the K step
     const int rb = ptid >> 2;  // base row 0..63
 
-    int a_y0[AR], a_x0[AR], a_base[AR];
+    IGemmRows<AR> rows;
     int b_off[BR];
-    const int plane = p.Cd * p.Kpad;
+    const int plane = p.Cd * p.Kpad;  // bf16 elements per weight plane
     const int cp8 = p.Cs >> 3;
-    int cc = 0, kx = 0, ky = 0;
+    IGemmCursor<4> cur;
     int lt_tile = 0, lt_kt = 0;  // load cursor: (index among my tiles, K step) of the next load_tiles call
 
     auto begin_tile = [&](int i) {
       const int bid = xcd_remap((int)blockIdx.x + i * (int)gridDim.x, ntiles);
       const int tile_n = bid % p.tiles_n;
       const int tile_m = bid / p.tiles_n;
-      const int m0 = tile_m * BM, n0 = tile_n * BN;
 #pragma unroll
-      for (int j = 0; j < AR; ++j) {
-        const int m = m0 + rb + 64 * j;
-        if (m < p.M) {
-          const int hw = p.Hm * p.Wm;
-          const int n = m / hw;
-          const int rem = m - n * hw;
-          const int gy = rem / p.Wm;
-          const int gx = rem - gy * p.Wm;
-          a_y0[j] = gy * p.ash + p.oy0;
-          a_x0[j] = gx * p.asw + p.ox0;
-          a_base[j] = ((n * p.Hs + a_y0[j]) * p.Ws + a_x0[j]) * p.Cs;
-        } else {
-          a_y0[j] = -(1 << 28);
-          a_x0[j] = 0;
-          a_base[j] = 0;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < BR; ++j) {
-        int co = n0 + rb + 64 * j;
-        co = co < p.Cd ? co : p.Cd - 1;
-        b_off[j] = co * p.Kpad + c4 * 8;
-      }
-      const int tap = c4 / cp8;
-      cc = c4 - tap * cp8;
-      ky = tap / p.kw;
-      kx = tap - ky * p.kw;
+      for (int j = 0; j < AR; ++j) rows.decode(p, j, tile_m * BM + rb + 64 * j);
+      weight_rows_decode(p, tile_n * BN + rb, c4, b_off);
+      cur.seek(c4, cp8, p.kw);
     };
 
     // two register sets: the loads of step t+2 are issued before step t+1's registers are consumed, so a
@@ -103,74 +77,19 @@ __global__ __launch_bounds__(512) void conv_igemm_x3ws_kernel(const IGemmArgs p)
     auto load_tiles = [&](auto SET) {
       constexpr int s = decltype(SET)::value;
       if (lt_kt == 0) begin_tile(lt_tile);
-      const int kt = lt_kt;
-      okmask[s] = 0;
-      const bool kvalid = ky < p.kh;
-      const int oy = ky * p.oys, ox = kx * p.oxs;
-      const int tapoff = (oy * p.Ws + ox) * p.Cs + cc * 8;
-#pragma unroll
-      for (int j = 0; j < AR; ++j) {
-        const int sy = a_y0[j] + oy, sx = a_x0[j] + ox;
-        const bool ok = kvalid && (unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws;
-        okmask[s] |= ok ? (1u << j) : 0u;
-        const float* src = p.src + (ok ? a_base[j] + tapoff : 0);
-        ra[s][j][0] = *reinterpret_cast<const f32x4*>(src);
-        ra[s][j][1] = *reinterpret_cast<const f32x4*>(src + 4);
-      }
-#pragma unroll
-      for (int j = 0; j < BR; ++j)
-#pragma unroll
-        for (int pt = 0; pt < NP; ++pt)
-          rbv[s][j][pt] = *reinterpret_cast<const u32x4*>(p.wgt3 + (size_t)pt * plane + b_off[j] + kt * BK3);
-      if (cp8 >= 4) {
-        cc += 4;
-        const bool wrap = cc >= cp8;
-        cc = wrap ? cc - cp8 : cc;
-        kx += wrap ? 1 : 0;
-        const bool wrapx = kx == p.kw;
-        kx = wrapx ? 0 : kx;
-        ky += wrapx ? 1 : 0;
-      } else {
-        const int q = (kt + 1) * 4 + c4;
-        const int tap = q / cp8;
-        cc = q - tap * cp8;
-        ky = tap / p.kw;
-        kx = tap - ky * p.kw;
-      }
+      okmask[s] = igemm_gather<8>(p, rows, cur, ra[s]);
+      weight_rows_load<NP>(p, b_off, plane, lt_kt, rbv[s]);
+      cur.advance(lt_kt, c4, cp8, p.kw);
       if (++lt_kt == nk) {
         lt_kt = 0;
         ++lt_tile;
       }
     };
-
     auto store_tiles = [&](auto SET, int stage) {
       constexpr int s = decltype(SET)::value;
       unsigned char* Ab = smem3 + stage * kStage;
-      unsigned char* Bb = Ab + 3 * BM * kRowBytes;
-#pragma unroll
-      for (int j = 0; j < AR; ++j) {
-        const int row = rb + 64 * j;
-        const int off = plane_off(row, c4);
-        const bool ok = (okmask[s] >> j) & 1u;
-        u32x4 H, M, L;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const f32x4 v = ra[s][j][e >> 1];
-          const float x0 = ok ? v[2 * (e & 1)] : 0.f, x1 = ok ? v[2 * (e & 1) + 1] : 0.f;
-          uint32_t h, m = 0, l = 0;
-          split_op<NP, PK>(x0, x1, a_inv, h, m, l);
-          H[e] = h; M[e] = m; L[e] = l;
-        }
-        *reinterpret_cast<u32x4*>(Ab + off) = H;
-        if (NP >= 2) *reinterpret_cast<u32x4*>(Ab + BM * kRowBytes + off) = M;
-        if (NP == 3) *reinterpret_cast<u32x4*>(Ab + 2 * BM * kRowBytes + off) = L;
-      }
-#pragma unroll
-      for (int j = 0; j < BR; ++j) {
-        const int off = plane_off(rb + 64 * j, c4);
-#pragma unroll
-        for (int pt = 0; pt < NP; ++pt) *reinterpret_cast<u32x4*>(Bb + pt * BN * kRowBytes + off) = rbv[s][j][pt];
-      }
+      split_store_rows<NP, PK>(ra[s], okmask[s], Ab, kAPlane, rb, c4, a_inv);
+      weight_rows_store<NP>(rbv[s], Ab + 3 * kAPlane, kBPlane, rb, c4);
     };
 
     using S0 = std::integral_constant<int, 0>;
@@ -211,7 +130,7 @@ __global__ __launch_bounds__(512) void conv_igemm_x3ws_kernel(const IGemmArgs p)
 
   f32x16 acc[MB][NB];
 
-  int fa_off[MB][2], fb_off[NB][2];
+  int fa_off[MB][2], fb_off[NB][2];   // from the stage's base: the weight planes follow the three activation planes
 #pragma unroll
   for (int a = 0; a < MB; ++a)
 #pragma unroll
@@ -219,33 +138,15 @@ __global__ __launch_bounds__(512) void conv_igemm_x3ws_kernel(const IGemmArgs p)
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-      fb_off[b][kk] = 3 * BM * kRowBytes + plane_off(wn * WN + b * 32 + li, 2 * kk + lh);
+    for (int kk = 0; kk < 2; ++kk) fb_off[b][kk] = 3 * kAPlane + plane_off(wn * WN + b * 32 + li, 2 * kk + lh);
 
   float out_scale = 1.f;   // f16x2: activation scale x weight scale
   if constexpr (NP == 2) out_scale = op_scale(act_absmax(p.a_scale)).s * op_scale(*p.w_scale).s;
-  bf16x8 fa[2][MB][3], fb[2][NB][3];  // fragment registers, double buffered across the two k-halves
+  bf16x8 fa[2][MB][3], fb[2][NB][3];   // fragment registers, double buffered across the two k-halves
   auto read_frags = [&](const unsigned char* S, int kk, int slot) {
-#pragma unroll
-    for (int a = 0; a < MB; ++a)
-#pragma unroll
-      for (int pt = 0; pt < NP; ++pt)
-        fa[slot][a][pt] = *reinterpret_cast<const bf16x8*>(S + pt * BM * kRowBytes + fa_off[a][kk]);
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int pt = 0; pt < NP; ++pt)
-        fb[slot][b][pt] = *reinterpret_cast<const bf16x8*>(S + pt * BN * kRowBytes + fb_off[b][kk]);
+    frag_read<NP, kAPlane, kBPlane>(fa[slot], fb[slot], S, S, fa_off, fb_off, kk);
   };
-  auto mfmas = [&](int slot) {
-#pragma unroll
-    for (int t = 0; t < X3Prod<NP>::N; ++t)
-#pragma unroll
-      for (int a = 0; a < MB; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-          acc[a][b] = mfma_np<NP>(fb[slot][b][x3_pb(NP, t)], fa[slot][a][x3_pa(NP, t)], acc[a][b]);
-  };
+  auto mfmas = [&](int slot) { frag_mma<NP>(acc, fa[slot], fb[slot]); };
 
   __syncthreads();
   int g = 0;
@@ -281,53 +182,24 @@ __global__ __launch_bounds__(512) void conv_igemm_x3ws_kernel(const IGemmArgs p)
   if (p.out_amax) amax_commit(p.out_amax, amax_l.m);   // once per wave, over all the tiles of this workgroup
 }
 
-// persistent workgroups, and the wave-specialised form also for short reductions (one tile per workgroup with the short
-// reductions on the single-role kernel: 3-9 % behind on the K <= 512 layers with Cd >= 128)
-static constexpr int ws_persist() { return 1; }
-
-template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE, int NP>
-static int launch_ws_np(IGemmArgs& a, hipStream_t stream) {
-  a.tiles_m = ceil_div(a.M, BM);
-  a.tiles_n = ceil_div(a.Cd, BN);
-  bn_stats_setup(a, BM, BN, WAVES_M, a.tiles_m);
-  const size_t lds = (size_t)NSTAGE * 3 * (BM + BN) * kRowBytes;   // >= the statistics epilogue's scratch
-  a.bn_scratch_off = 0;
-  static PerDeviceOnce attr_once;
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_x3ws_kernel<BM, BN, WAVES_M, WAVES_N, NSTAGE, NP>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  const long long nwg = (long long)a.tiles_m * a.tiles_n;
-  if (nwg <= 0 || nwg > 0x7fffffffLL) {
-    set_error("conv_igemm_x3ws: bad grid %lld", nwg);
-    return EVK_E_INVALID;
-  }
+// Persistent workgroups, and the wave-specialised form also for short reductions (one tile per workgroup with the short
+// reductions on the single-role kernel: 3-9 % behind on the K <= 512 layers with Cd >= 128).
+int launch_igemm_x3ws(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
+  EVK_REQUIRE(igemm_x3_supports(a) && r.bm == 128 && r.stages == 2, EVK_E_INVALID, "conv_igemm_x3ws: routed a launch it cannot take");
+  EVK_REQUIRE(r.bn == 256 || r.bn == 128 || r.bn == 64, EVK_E_INVALID, "conv_igemm_x3ws: no 128 x %d tile", r.bn);
+  a.bn_scratch_off = 0;   // the ring (>= the statistics epilogue's scratch) serves as the scratch
   // one workgroup per CU (LDS), each walking ceil(tiles / 256) tiles; 256 is a multiple of 8, so a workgroup's
   // tiles stay on its XCD under the remap
   // statistics mode: one tile per workgroup (the epilogue parks the tile in the LDS ring, which a persistent
   // workgroup's staging waves would already be refilling)
-  const unsigned grid = (ws_persist() && nwg > 256 && !a.bn_part) ? 256u : (unsigned)nwg;
-  hipLaunchKernelGGL((conv_igemm_x3ws_kernel<BM, BN, WAVES_M, WAVES_N, NSTAGE, NP>), dim3(grid), dim3(512), lds, stream, a);
-  return check_launch("conv_igemm_x3ws");
-}
-
-template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE>
-static int launch_ws(IGemmArgs& a, hipStream_t stream) {
-  if (a.planes == 1) return launch_ws_np<BM, BN, WAVES_M, WAVES_N, NSTAGE, 1>(a, stream);
-  if (a.planes == 2)
-    return a.a_packed ? launch_ws_np<BM, BN, WAVES_M, WAVES_N, NSTAGE, 4>(a, stream)
-                      : launch_ws_np<BM, BN, WAVES_M, WAVES_N, NSTAGE, 2>(a, stream);
-  return launch_ws_np<BM, BN, WAVES_M, WAVES_N, NSTAGE, 3>(a, stream);
-}
-
-int launch_igemm_x3ws(IGemmArgs& a, const ConvRoute& r, hipStream_t stream) {
-  EVK_REQUIRE(igemm_x3_supports(a) && r.bm == 128 && r.stages == 2, EVK_E_INVALID, "conv_igemm_x3ws: routed a launch it cannot take");
-  switch (r.bn) {
-    case 256: return launch_ws<128, 256, 2, 2, 2>(a, stream);
-    case 128: return launch_ws<128, 128, 2, 2, 2>(a, stream);
-    case 64: return launch_ws<128, 64, 2, 2, 2>(a, stream);
-  }
-  EVK_REQUIRE(false, EVK_E_INVALID, "conv_igemm_x3ws: no 128 x %d tile", r.bn);
+  auto grid = [&](long long tiles) { return (tiles > 256 && !a.bn_part) ? 256 : tiles; };
+  return pick<256, 128, 64>(r.bn, [&](auto BN) {
+    return pick_npx(a, [&](auto NPX) {
+      constexpr int bn = decltype(BN)::value;
+      return launch_igemm_tile<&conv_igemm_x3ws_kernel<128, bn, 2, 2, 2, decltype(NPX)::value>>(
+          a, stream, "conv_igemm_x3ws", 128, bn, 2, 512, (size_t)2 * 3 * (128 + bn) * kRowBytes, 0, grid);
+    });
+  });
 }
 
 }  // namespace evk

@@ -306,8 +306,7 @@ ConvRoute route_conv(const IGemmArgs& a, bool split, const RouteKnobs& k, int cu
 // ---- the route as a kernel trace spells it --------------------------------------------------------------------------
 void route_kernel_name(const IGemmArgs& a, const ConvRoute& r, char* buf, size_t n) {
   const char* pk = a.a_packed ? "true" : "false";
-  // operand form of the split kernels' NP / NPX parameter: 1 bf16, 2 f16x2, 4 f16x2 with packed activations, 3 bf16x3
-  const int np = a.planes == 1 ? 1 : a.planes == 2 ? (a.a_packed ? 4 : 2) : 3;
+  const int np = x3_npx(a);   // what the launchers dispatch on (pick_npx)
   switch (r.kernel) {
     case ConvKernel::Igemm:
       snprintf(buf, n, "conv_igemm_kernel<%d, %d, %d, %d>", r.bm, r.bn, r.bm == 256 ? 4 : 2, r.bm == 256 ? 1 : 2);

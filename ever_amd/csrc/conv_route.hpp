@@ -22,8 +22,8 @@
 namespace evk {
 
 enum class ConvKernel {
-  Igemm,    // conv_igemm.hip: fp32 implicit GEMM
-  SmallM,   // conv_igemm.hip: conv1x1_smallm (1x1 on a handful of rows)
+  Igemm,    // conv_igemm_f32.hip: fp32 implicit GEMM
+  SmallM,   // conv_igemm_f32.hip: conv1x1_smallm (1x1 on a handful of rows)
   Wino,     // conv3x3_wino_x3.hip
   Halo,     // conv3x3_halo_x3.hip
   C1Ps2,    // conv1x1_ps2.hip
@@ -78,6 +78,14 @@ inline PlaneLayout desc_layout(const evk_conv_desc* d, int for_dgrad, int planes
   IGemmArgs a = for_dgrad ? igemm_geometry_dgrad(d, 0, 0) : igemm_geometry_fwd(d);
   a.planes = planes;
   return route_layout(a, route_knobs());
+}
+
+// Operand form of the split kernels' NP / NPX template parameter (x3_common.hpp: X3Mode): 1 bf16, 2 f16x2, 4 f16x2 with
+// packed activations, 3 bf16x3.  ONE mapping for the launchers (pick_npx) and for route_kernel_name.
+inline int x3_npx(const IGemmArgs& a) { return a.planes == 1 ? 1 : a.planes == 2 ? (a.a_packed ? 4 : 2) : 3; }
+template <typename F>
+inline int pick_npx(const IGemmArgs& a, F&& f) {   // f(std::integral_constant<int, NPX>)
+  return pick<1, 2, 4, 3>(x3_npx(a), f);
 }
 
 // launchers: tiles_m/n, statistics setup, LDS size and grid of the instantiation the route names.  A route the kernel

@@ -3,7 +3,7 @@
 //   dw[co][k] = sum_m dy[m][co] * im2col(x)[m][k]        m = (n, oy, ox),  k = (ky, kx, ci)
 //
 // Replaces aten::convolution_backward(weight, bias) of the nn.Conv2d sites listed in
-// conv_igemm.hip (reference ever/module/_resnets.py:21-29,149 ; fpn.py ; fs_relation.py).
+// conv_igemm_f32.hip (reference ever/module/_resnets.py:21-29,149 ; fpn.py ; fs_relation.py).
 //
 // GEMM view: rows = Cout, cols = kh*kw*Cin, reduction = pixels.  Both operands are stored
 // pixel-major in HBM ([pixel][channel]), which is exactly the k-major LDS image the f32 MFMA

@@ -342,6 +342,34 @@ inline void bn_stats_setup(IGemmArgs& a, int BM, int BN, int WAVES_M, long long 
   a.bn_parts = (int)parts;
 }
 
+// Launch of a tile kernel of the family — conv_igemm_f32 / _x3 / _x3ws.hip and the one-tap ring kernels (c1_tile.hpp): the
+// bm x bn tiles, the statistics setup (row_waves = row waves per tile; 0: the kernel has no statistics epilogue), LDS = the
+// larger of the operand ring and the statistics epilogue's scratch (which reuses the ring), the attribute, the grid check and
+// the launch.  A template on the kernel: the once-per-device attribute flag is one per instantiation.
+// grid(tiles): workgroups to launch, asked after the statistics setup; extra: the kernel's arguments after IGemmArgs.
+struct OneWorkgroupPerTile {
+  long long operator()(long long tiles) const { return tiles; }
+};
+template <auto Kern, typename Grid = OneWorkgroupPerTile, typename... Extra>
+int launch_igemm_tile(IGemmArgs& a, hipStream_t stream, const char* name, int bm, int bn, int row_waves, int block, size_t ring,
+                      size_t stats_scratch, Grid grid = {}, Extra... extra) {
+  a.tiles_m = ceil_div(a.M, bm);
+  a.tiles_n = ceil_div(a.Cd, bn);
+  if (row_waves) bn_stats_setup(a, bm, bn, row_waves, a.tiles_m);
+  const size_t lds = ring < stats_scratch ? stats_scratch : ring;
+  static PerDeviceOnce attr_once;
+  if (attr_once.first()) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  }
+  const long long nwg = (long long)a.tiles_m * a.tiles_n;
+  if (nwg <= 0 || nwg > 0x7fffffffLL) {
+    set_error("%s: bad grid %lld", name, nwg);
+    return EVK_E_INVALID;
+  }
+  hipLaunchKernelGGL(Kern, dim3((unsigned)grid(nwg)), dim3(block), lds, stream, a, extra...);
+  return check_launch(name);
+}
+
 inline int kpad32(int k) { return (k + 31) & ~31; }   // K of a weight-plane row: whole 32-element steps, zero padded
 
 int launch_split_weight_wino(const float* w, uint16_t* out, int Cout, int Cin, int for_dgrad, hipStream_t st,

@@ -1,7 +1,6 @@
 // Host side of the weight-gradient family: arguments, plan, route and the launchers' prototypes (device pieces: wgrad_tile.hpp).
 #pragma once
 #include "common.hpp"
-#include <type_traits>
 
 namespace evk {
 
@@ -63,18 +62,5 @@ constexpr uint32_t kWGradFlags = EVK_CONV_X_PACKED | EVK_CONV_DY_PACKED | EVK_CO
 // column sums of a [rows][c] fp32 matrix (bias gradients; conv_wgrad.hip): also used by conv_transpose.hip
 size_t colsum_workspace_bytes(int64_t rows, int c);
 int launch_colsum(const float* src, float* out, int64_t rows, int c, float* workspace, hipStream_t st);
-
-// Run-time value -> template argument: f(std::integral_constant<int, V>{}) for the listed V that equals v, the LAST one when
-// none does.
-template <int V0, int... Vs, typename F>
-inline int pick(int v, F&& f) {
-  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
-  else return v == V0 ? f(std::integral_constant<int, V0>{}) : pick<Vs...>(v, f);
-}
-// the (bm, bn) tiles of the single-role kernels: f(BM, BN)
-template <typename F>
-inline int pick_tile(int bm, int bn, F&& f) {
-  return pick<128, 64>(bm, [&](auto BM) { return pick<128, 64>(bn, [&](auto BN) { return f(BM, BN); }); });
-}
 
 }  // namespace evk

@@ -46,6 +46,10 @@ GENERIC_CASES = [
     # g1 with Cout a whole number of tiles of every width: the statistics epilogue needs Cd % BN == 0 (bn_stats_setup), so it
     # never engages on g1 / g4.  w64: 268 tiles, one per workgroup in statistics mode.
     _g('g6', 2, 65, 65, 72, 256, 1, raw=True, stats=True),
+    # three 8-channel chunks per tap, forward and data gradient alike: a 32-element K step spans taps of a multi-tap filter
+    # (the K cursor re-derives its tap by division with kw > 1: g4 is 1x1, g5 has 5 chunks per tap).  K = 216 of Kpad 224;
+    # four row tiles of 128, the last holds 53 rows
+    _g('g7', 1, 19, 23, 24, 24, 3, p=1, bias=True),
 ]
 
 # ---- halo family: conv3x3_halo_x3.hip, all 3x3 stride 1 pad 1 -------------------------------------------------------------
@@ -72,7 +76,7 @@ HALO_CASES = [
     _g('h6', 1, 48, 40, 72, 128, 3, p=1, bias=True, fwd='every', dgrad='every', raw=True, stats=True),
 ]
 
-# ---- fp32 family: conv_igemm.hip, route_fp32 is a pure rule (no switch) ---------------------------------------------------
+# ---- fp32 family: conv_igemm_f32.hip, route_fp32 is a pure rule (no switch) ---------------------------------------------------
 FP32_CASES = [   # (case, forward instantiation, data-gradient instantiation)
     (_g('f32_a', 1, 129, 127, 8, 520, 1), 'conv_igemm_kernel<128, 128, 2, 2>', 'conv_igemm_kernel<64, 64, 2, 2>'),
     (_g('f32_e', 1, 129, 127, 520, 8, 1), 'conv_igemm_kernel<64, 64, 2, 2>', 'conv_igemm_kernel<128, 128, 2, 2>'),

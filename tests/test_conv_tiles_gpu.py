@@ -1,5 +1,5 @@
 """Every forward / data-gradient tile form at ragged shapes against float64 (csrc/conv_igemm_x3ws.hip, conv_igemm_x3.hip,
-conv3x3_halo_x3.hip, conv_igemm.hip; reference call sites: the convolutions of ever/module/_resnets.py, fpn.py, farseg.py).
+conv3x3_halo_x3.hip, conv_igemm_f32.hip; reference call sites: the convolutions of ever/module/_resnets.py, fpn.py, farseg.py).
 
 The planner takes the large forms — the persistent wave-specialised kernel, 128-row single-role tiles, 128-wide halo tiles,
 16-row patches, eight matrix waves, the fp32 128 x 128 / 128 x 64 / 256 x 64 tiles — only from 256 or 512 workgroups on, so the
