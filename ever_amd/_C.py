@@ -116,6 +116,10 @@ SIGNATURES = {
     'evk_relation_bn_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_i32, c_i32, c_i32, P, c_size_t, P]),
     'evk_bn_bwd_from_partials': (c_int, [P, P, P, P, P, P, P, c_i32, P, P, P, c_i64, c_i32, c_u32, c_i32, P, c_size_t, P, P]),
     'evk_bn_bwd_bits': (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_i64, c_i32, c_u32, c_i32, P, c_size_t, P, P, P]),
+    'evk_bn_fwd_train_parts_dual': (c_int, [P, P, P, P, P, P, c_f32, c_f32, P, P, P, P, c_f32, c_f32, P, P, P, P, P, c_i64, c_i32,
+                                            P, c_i32, P, c_i32, P, c_size_t, P, P, P]),
+    'evk_bn_bwd_dual': (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_i64, c_i32, c_u32, c_u32, P, c_size_t, P, P, P, P]),
+    'evk_bn_bwd_dual_fused': (c_int, [c_u32, c_u32]),
     'evk_relu_fwd': (c_int, [P, P, c_i64, P]),
     'evk_relu_bwd': (c_int, [P, P, P, c_i64, P]),
     'evk_add': (c_int, [P, P, P, c_i64, P]),

@@ -261,14 +261,15 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
 
 // coef[0][C] = gamma*invstd ; coef[1][C] = mean(g) ; coef[2][C] = mean(g*xhat)  (0 when !train)
 // FC channels x 256 / FC lanes per workgroup: 8 x 32 by default; 2 x 128 (four times the workgroups) when the partials are many
-template <int FC = kFinCh>
-__global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restrict__ partial, int nblk, int C,
-                                                           double inv_rows, const float* __restrict__ gamma,
-                                                           const float* __restrict__ invstd,
-                                                           float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                           float* __restrict__ coef, int train,
-                                                           uint32_t* __restrict__ amax,
-                                                           const float* __restrict__ pmax) {
+// (the body is a function of its own so that bn_bwd_final_dual_kernel below can finish two BatchNorms in one launch)
+template <int FC>
+__device__ __forceinline__ void bn_bwd_final_body(const float* __restrict__ partial, int nblk, int C,
+                                                  double inv_rows, const float* __restrict__ gamma,
+                                                  const float* __restrict__ invstd,
+                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                  float* __restrict__ coef, int train,
+                                                  uint32_t* __restrict__ amax,
+                                                  const float* __restrict__ pmax) {
   // pmax == nullptr: stage 3 accumulates max|dx| into the slots (zeroed here).  pmax != nullptr (packed dx): the slots
   // arrive ZERO and every workgroup raises one of them to a bound of its channels' |dx| before stage 3 starts:
   //   |dx_c| = |k0 (g - k1 - xhat k2)| <= |k0| (max|g_c| + |k1| + max|xhat_c| |k2|)
@@ -318,6 +319,16 @@ __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restri
     // per thread — reads ONE word instead of folding 64 cache lines per wave (measured: the fold cost the pass 5 %)
     if (bits) atomicMax(&amax[0], bits);
   }
+}
+template <int FC = kFinCh>
+__global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restrict__ partial, int nblk, int C,
+                                                           double inv_rows, const float* __restrict__ gamma,
+                                                           const float* __restrict__ invstd,
+                                                           float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                           float* __restrict__ coef, int train,
+                                                           uint32_t* __restrict__ amax,
+                                                           const float* __restrict__ pmax) {
+  bn_bwd_final_body<FC>(partial, nblk, C, inv_rows, gamma, invstd, dgamma, dbeta, coef, train, amax, pmax);
 }
 
 // dx = coef0 * (g - coef1 - xhat*coef2); one 16-byte element per thread (see bn_apply_kernel), the per-channel
@@ -379,15 +390,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 // subset each, then the 32 lanes folded in index order — the same outputs as bn_stats_final_kernel, no pass over x.
 // FC channels x FL record lanes per workgroup (FC * FL = 256): 8 x 32 for the small maps; 2 x 128 where a channel has
 // hundreds of records (the 128^2 maps: 2048 per channel — at 32 lanes each lane walked 64 strided records: 9-47 us a launch)
+// (the body is a function of its own so that bn_parts_final_dual_kernel below can merge two BatchNorms' records in one launch)
 template <int FC, int FL>
-__global__ __launch_bounds__(256) void bn_parts_final_kernel(const float* __restrict__ parts, int nparts, int C,
-                                                             double rows, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta,
-                                                             float* __restrict__ running_mean,
-                                                             float* __restrict__ running_var, float momentum, float eps,
-                                                             float* __restrict__ save_mean, float* __restrict__ save_invstd,
-                                                             float* __restrict__ scale_shift,
-                                                             uint32_t* __restrict__ amax, int pack) {
+__device__ __forceinline__ void bn_parts_final_body(const float* __restrict__ parts, int nparts, int C,
+                                                    double rows, const float* __restrict__ gamma,
+                                                    const float* __restrict__ beta,
+                                                    float* __restrict__ running_mean,
+                                                    float* __restrict__ running_var, float momentum, float eps,
+                                                    float* __restrict__ save_mean, float* __restrict__ save_invstd,
+                                                    float* __restrict__ scale_shift,
+                                                    uint32_t* __restrict__ amax, int pack) {
   // pack == 0: the apply pass accumulates max|y| into the slots (zeroed here).  pack != 0 (y will be written packed,
   // EVK_BN_PACK_Y): the slots arrive ZERO and slot 0 is raised HERE to a bound of |y|, from the records alone: a row of
   // record i deviates from the record's mean by at most sqrt(M2_i) (one term of the sum), so
@@ -462,6 +474,47 @@ __global__ __launch_bounds__(256) void bn_parts_final_kernel(const float* __rest
     if (bits) atomicMax(&amax[0], bits);   // slot 0 alone: the apply pass reads one word (see bn_bwd_final_kernel)
   }
 }
+template <int FC, int FL>
+__global__ __launch_bounds__(256) void bn_parts_final_kernel(const float* __restrict__ parts, int nparts, int C,
+                                                             double rows, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta,
+                                                             float* __restrict__ running_mean,
+                                                             float* __restrict__ running_var, float momentum, float eps,
+                                                             float* __restrict__ save_mean, float* __restrict__ save_invstd,
+                                                             float* __restrict__ scale_shift,
+                                                             uint32_t* __restrict__ amax, int pack) {
+  bn_parts_final_body<FC, FL>(parts, nparts, C, rows, gamma, beta, running_mean, running_var, momentum, eps, save_mean,
+                              save_invstd, scale_shift, amax, pack);
+}
+
+// The two finalisations of a block end with a shortcut convolution in ONE launch each: blockIdx.y selects the BatchNorm, the
+// workgroups of a row do what the single kernels' workgroups do (bn_fin_group and zero_amax look at blockIdx.x alone).
+struct BnPartsFinalSet {
+  const float* parts;
+  int nparts;
+  const float *gamma, *beta;
+  float *running_mean, *running_var;
+  float momentum, eps;
+  float *save_mean, *save_invstd, *scale_shift;
+  uint32_t* amax;
+};
+template <int FC, int FL>
+__global__ __launch_bounds__(256) void bn_parts_final_dual_kernel(BnPartsFinalSet a, BnPartsFinalSet b, int C, double rows) {
+  const BnPartsFinalSet s = blockIdx.y ? b : a;
+  bn_parts_final_body<FC, FL>(s.parts, s.nparts, C, rows, s.gamma, s.beta, s.running_mean, s.running_var, s.momentum, s.eps,
+                              s.save_mean, s.save_invstd, s.scale_shift, s.amax, 0);
+}
+struct BnBwdFinalSet {
+  const float *partial, *gamma, *invstd;
+  float *dgamma, *dbeta, *coef;
+  uint32_t* amax;
+  const float* pmax;
+};
+__global__ __launch_bounds__(256) void bn_bwd_final_dual_kernel(BnBwdFinalSet a, BnBwdFinalSet b, int nblk, int C,
+                                                                double inv_rows) {
+  const BnBwdFinalSet s = blockIdx.y ? b : a;
+  bn_bwd_final_body<kFinCh>(s.partial, nblk, C, inv_rows, s.gamma, s.invstd, s.dgamma, s.dbeta, s.coef, 1, s.amax, s.pmax);
+}
 
 // (A one-launch backward for small maps — every thread's rows in registers across two grid-wide barriers, 3 tensor transfers
 // instead of 5 — lived here in rounds 2 and 3.  Its grid had to be resident as a whole, so it was off beside the weight-
@@ -503,6 +556,199 @@ static void launch_bn_apply(hipStream_t st, bool pack, const float* x, const flo
   EVK_BN_LAUNCH_PK(bn_apply_kernel, pack, dim3(oneshot_grid(n4)), 0, st, x, residual, scale_shift, y, n4, C,
                    (flags & EVK_BN_RELU) ? 1 : 0, amax, relu_bits);
 }
+
+// ---- The end of a residual block whose shortcut is a convolution (`layerN.0`): out = relu(bn_a(za) + bn_b(zb)), za the
+// main branch's last convolution output, zb the shortcut convolution's.  The passes below take BOTH maps, so the shortcut's
+// normalised copy yb = bn_b(zb) is never stored: forward 3 transfers of the map instead of 5, backward reduce 3 instead of 4,
+// backward apply 5 instead of 6.  New kernels only: the single-map kernels above keep their code.
+
+// y = relu((za*sca + sha) + (zb*scb + shb)), ReLU bits, max|y|: bn_apply_kernel's residual form with the residual computed in
+// registers.  The shortcut term is an expression of its own, so it is rounded as the stored yb was (one fused multiply-add)
+// before the add.
+__global__ __launch_bounds__(256) void bn_apply_dual_kernel(const float* __restrict__ za, const float* __restrict__ zb,
+                                                            const float* __restrict__ scale_shift_a,
+                                                            const float* __restrict__ scale_shift_b, float* __restrict__ y,
+                                                            size_t n4, int C, uint32_t* __restrict__ amax,
+                                                            uint32_t* __restrict__ relu_bits) {
+  const size_t base = (size_t)bn_blk() * 256;
+  const size_t i = base + threadIdx.x;
+  const bool valid = i < n4;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (valid) {
+    const int c4 = C >> 2;
+    const int cb = chunk_of(base, c4);
+    const f32x4 sca = reinterpret_cast<const f32x4*>(scale_shift_a)[cb];
+    const f32x4 sha = reinterpret_cast<const f32x4*>(scale_shift_a + C)[cb];
+    const f32x4 scb = reinterpret_cast<const f32x4*>(scale_shift_b)[cb];
+    const f32x4 shb = reinterpret_cast<const f32x4*>(scale_shift_b + C)[cb];
+    const f32x4 yb = bn_ld(zb, i) * scb + shb;
+    v = bn_ld(za, i) * sca + sha;
+    v += yb;
+  }
+  // every lane of a wave takes part (v = 0 where the element does not exist); a wave wholly past the end has no chunk
+  if (((i >> 6) << 6) < n4) relu_bits_store(relu_bits, i >> 6, v.x > 0.f, v.y > 0.f, v.z > 0.f, v.w > 0.f);
+  if (valid) {
+    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    reinterpret_cast<f32x4*>(y)[i] = v;
+  }
+  if (amax) block_absmax(v, valid, amax);   // all lanes of the workgroup arrive here together
+}
+
+// Backward stage 1 for both maps: g = dy where the block's ReLU bit is set, masked ONCE;
+// partial_a[blk] = (sum g, sum g * xhat_a), partial_b[blk] = (sum g, sum g * xhat_b) — bn_bwd_partial_kernel's plan, row
+// order and fold, so each record has the bits the single-map pass gives.  PK: pmax_a / pmax_b as bn_bwd_partial_kernel<true>.
+template <bool PK>
+__global__ __launch_bounds__(256) void bn_bwd_partial_dual_kernel(
+    const float* __restrict__ dy, const float* __restrict__ xa, const float* __restrict__ xb,
+    const float* __restrict__ mean_a, const float* __restrict__ invstd_a, const float* __restrict__ mean_b,
+    const float* __restrict__ invstd_b, float* __restrict__ partial_a, float* __restrict__ partial_b, int64_t rows, int C,
+    int64_t rows_per_blk, int tpc, int rl, float* __restrict__ pmax_a, float* __restrict__ pmax_b,
+    const uint32_t* __restrict__ bits) {
+  __shared__ f32x4 red[2][256];
+  const int c4 = C >> 2;
+  const int tc = threadIdx.x % tpc, tr = threadIdx.x / tpc;
+  const int64_t r0 = (int64_t)bn_blk() * rows_per_blk;
+  const int64_t r1 = min(rows, r0 + rows_per_blk);
+  for (int cb = tc; cb < c4; cb += tpc) {
+    const f32x4 mua = *reinterpret_cast<const f32x4*>(mean_a + cb * 4);
+    const f32x4 isa = *reinterpret_cast<const f32x4*>(invstd_a + cb * 4);
+    const f32x4 mub = *reinterpret_cast<const f32x4*>(mean_b + cb * 4);
+    const f32x4 isb = *reinterpret_cast<const f32x4*>(invstd_b + cb * 4);
+    f32x4 s = {0.f, 0.f, 0.f, 0.f}, qa = {0.f, 0.f, 0.f, 0.f}, qb = {0.f, 0.f, 0.f, 0.f};
+    f32x4 gm = {0.f, 0.f, 0.f, 0.f}, xma = {0.f, 0.f, 0.f, 0.f}, xmb = {0.f, 0.f, 0.f, 0.f};
+    if (tr < rl) {
+      auto one = [&](const f32x4 gin, const f32x4 xva, const f32x4 xvb, size_t off) {
+        const f32x4 g = relu_bits_mask(gin, bits, off >> 2);
+        s += g;
+        const f32x4 xha = (xva - mua) * isa;
+        qa += g * xha;
+        const f32x4 xhb = (xvb - mub) * isb;
+        qb += g * xhb;
+        if constexpr (PK) {
+          gm.x = fmaxf(gm.x, fabsf(g.x)); gm.y = fmaxf(gm.y, fabsf(g.y));
+          gm.z = fmaxf(gm.z, fabsf(g.z)); gm.w = fmaxf(gm.w, fabsf(g.w));
+          xma.x = fmaxf(xma.x, fabsf(xha.x)); xma.y = fmaxf(xma.y, fabsf(xha.y));
+          xma.z = fmaxf(xma.z, fabsf(xha.z)); xma.w = fmaxf(xma.w, fabsf(xha.w));
+          xmb.x = fmaxf(xmb.x, fabsf(xhb.x)); xmb.y = fmaxf(xmb.y, fabsf(xhb.y));
+          xmb.z = fmaxf(xmb.z, fabsf(xhb.z)); xmb.w = fmaxf(xmb.w, fabsf(xhb.w));
+        }
+      };
+      int64_t r = r0 + tr;
+      const int64_t st = rl;
+      // four rows per trip: 12 independent 16-byte loads in flight per lane
+      for (; r + 3 * st < r1; r += 4 * st) {
+        const size_t o0 = (size_t)r * C + cb * 4, o1 = (size_t)(r + st) * C + cb * 4;
+        const size_t o2 = (size_t)(r + 2 * st) * C + cb * 4, o3 = (size_t)(r + 3 * st) * C + cb * 4;
+        const f32x4 g0 = bp_ld(dy + o0), g1 = bp_ld(dy + o1);
+        const f32x4 g2 = bp_ld(dy + o2), g3 = bp_ld(dy + o3);
+        const f32x4 a0 = bp_ld(xa + o0), a1 = bp_ld(xa + o1);
+        const f32x4 a2 = bp_ld(xa + o2), a3 = bp_ld(xa + o3);
+        const f32x4 b0 = bp_ld(xb + o0), b1 = bp_ld(xb + o1);
+        const f32x4 b2 = bp_ld(xb + o2), b3 = bp_ld(xb + o3);
+        one(g0, a0, b0, o0);
+        one(g1, a1, b1, o1);
+        one(g2, a2, b2, o2);
+        one(g3, a3, b3, o3);
+      }
+      for (; r < r1; r += st) {
+        const size_t o0 = (size_t)r * C + cb * 4;
+        one(bp_ld(dy + o0), bp_ld(xa + o0), bp_ld(xb + o0), o0);
+      }
+    }
+    fold_store_record(red, s, qa, partial_a, bn_blk(), C, cb, tc, tr, tpc, rl);
+    fold_store_record(red, s, qb, partial_b, bn_blk(), C, cb, tc, tr, tpc, rl);
+    if constexpr (PK) {
+      red[0][threadIdx.x] = gm;
+      red[1][threadIdx.x] = xma;
+      __syncthreads();
+      if (tr == 0) {
+        for (int k = 1; k < rl; ++k) {
+          const f32x4 a = red[0][k * tpc + tc], b = red[1][k * tpc + tc];
+          gm.x = fmaxf(gm.x, a.x); gm.y = fmaxf(gm.y, a.y); gm.z = fmaxf(gm.z, a.z); gm.w = fmaxf(gm.w, a.w);
+          xma.x = fmaxf(xma.x, b.x); xma.y = fmaxf(xma.y, b.y); xma.z = fmaxf(xma.z, b.z); xma.w = fmaxf(xma.w, b.w);
+        }
+      }
+      __syncthreads();
+      red[0][threadIdx.x] = xmb;
+      __syncthreads();
+      if (tr == 0) {
+        for (int k = 1; k < rl; ++k) {
+          const f32x4 b = red[0][k * tpc + tc];
+          xmb.x = fmaxf(xmb.x, b.x); xmb.y = fmaxf(xmb.y, b.y); xmb.z = fmaxf(xmb.z, b.z); xmb.w = fmaxf(xmb.w, b.w);
+        }
+        float* oa = pmax_a + (size_t)bn_blk() * 2 * C;
+        float* ob = pmax_b + (size_t)bn_blk() * 2 * C;
+        *reinterpret_cast<f32x4*>(oa + cb * 4) = gm;
+        *reinterpret_cast<f32x4*>(oa + C + cb * 4) = xma;
+        *reinterpret_cast<f32x4*>(ob + cb * 4) = gm;
+        *reinterpret_cast<f32x4*>(ob + C + cb * 4) = xmb;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// Backward stage 3 for both maps: dxa = ka0 * (g - ka1 - xhat_a*ka2), dxb likewise from the second coefficient set; g is
+// read and masked once.  PKA / PKB: that output packed under the bound its finalisation left in slot 0 of its `amax`.
+template <bool PKA, bool PKB>
+__global__ __launch_bounds__(256) void bn_bwd_apply_dual_kernel(
+    const float* __restrict__ dy, const float* __restrict__ xa, const float* __restrict__ xb,
+    const float* __restrict__ mean_a, const float* __restrict__ invstd_a, const float* __restrict__ coef_a,
+    const float* __restrict__ mean_b, const float* __restrict__ invstd_b, const float* __restrict__ coef_b,
+    float* __restrict__ dxa, float* __restrict__ dxb, size_t n4, int C, uint32_t* __restrict__ amax_a,
+    uint32_t* __restrict__ amax_b, const uint32_t* __restrict__ bits) {
+  const size_t base = (size_t)bn_blk() * 256;
+  const size_t i = base + threadIdx.x;
+  const bool valid = i < n4;
+  f32x4 outa = {0.f, 0.f, 0.f, 0.f}, outb = {0.f, 0.f, 0.f, 0.f};
+  float pk_inv_a = 1.f, pk_inv_b = 1.f;
+  if constexpr (PKA) pk_inv_a = op_scale(amax_a[0]).inv;
+  if constexpr (PKB) pk_inv_b = op_scale(amax_b[0]).inv;
+  if (valid) {
+    const int c4 = C >> 2;
+    const int c = chunk_of(base, c4);
+    const f32x4 g = relu_bits_mask(bn_ld(dy, i), bits, i);
+    {
+      const f32x4 k0 = reinterpret_cast<const f32x4*>(coef_a)[c];
+      const f32x4 k1 = reinterpret_cast<const f32x4*>(coef_a + C)[c];
+      const f32x4 k2 = reinterpret_cast<const f32x4*>(coef_a + 2 * C)[c];
+      const f32x4 mu = reinterpret_cast<const f32x4*>(mean_a)[c];
+      const f32x4 is = reinterpret_cast<const f32x4*>(invstd_a)[c];
+      const f32x4 xh = (bn_ld(xa, i) - mu) * is;
+      outa = k0 * (g - k1 - xh * k2);
+      if constexpr (PKA) {
+        reinterpret_cast<u32x4*>(dxa)[i] = pack_hl4(outa, pk_inv_a);
+      } else {
+        reinterpret_cast<f32x4*>(dxa)[i] = outa;
+      }
+    }
+    {
+      const f32x4 k0 = reinterpret_cast<const f32x4*>(coef_b)[c];
+      const f32x4 k1 = reinterpret_cast<const f32x4*>(coef_b + C)[c];
+      const f32x4 k2 = reinterpret_cast<const f32x4*>(coef_b + 2 * C)[c];
+      const f32x4 mu = reinterpret_cast<const f32x4*>(mean_b)[c];
+      const f32x4 is = reinterpret_cast<const f32x4*>(invstd_b)[c];
+      const f32x4 xh = (bn_ld(xb, i) - mu) * is;
+      outb = k0 * (g - k1 - xh * k2);
+      if constexpr (PKB) {
+        reinterpret_cast<u32x4*>(dxb)[i] = pack_hl4(outb, pk_inv_b);
+      } else {
+        reinterpret_cast<f32x4*>(dxb)[i] = outb;
+      }
+    }
+  }
+  // all lanes of the workgroup arrive here together; block_absmax's LDS words are free again after the barrier between
+  if constexpr (!PKA)
+    if (amax_a) block_absmax(outa, valid, amax_a);
+  if constexpr (!PKA && !PKB) __syncthreads();
+  if constexpr (!PKB)
+    if (amax_b) block_absmax(outb, valid, amax_b);
+}
+
+// The (packed dz of the main branch, packed dz of the shortcut) forms of bn_bwd_apply_dual_kernel that exist: what the
+// ResNet-50 / ResNet-18 blocks produce — both packed (the f16x2 default), both plain (another arithmetic, observers), plain
+// main + packed shortcut (a BasicBlock whose 3x3 takes the planar weight gradient).  The fourth takes the two-call path.
+static bool bn_dual_fused(bool pack_a, bool pack_b) { return !(pack_a && !pack_b); }
 
 }  // namespace evk
 
@@ -659,6 +905,111 @@ extern "C" int evk_bn_bwd(const float* dy, const float* x, const float* y, const
                           void* workspace, size_t workspace_bytes, uint32_t* dx_absmax, void* stream) {
   return evk_bn_bwd_bits(dy, x, y, gamma, beta, save_mean, save_invstd, dx, d_residual, dgamma, dbeta, rows, C, flags, train,
                          workspace, workspace_bytes, dx_absmax, nullptr, stream);
+}
+
+// ---- Both BatchNorms at the end of a residual block with a shortcut convolution (bn_apply_dual_kernel and its neighbours).
+// Training mode, both statistics from epilogue records.  workspace: TWO single-map workspaces back to back
+// (2 * evk_bn_workspace_bytes): the main branch's records and coefficients in the first, the shortcut's in the second.
+extern "C" int evk_bn_fwd_train_parts_dual(const float* za, const float* zb, const float* gamma_a, const float* beta_a,
+                                           float* running_mean_a, float* running_var_a, float momentum_a, float eps_a,
+                                           const float* gamma_b, const float* beta_b, float* running_mean_b,
+                                           float* running_var_b, float momentum_b, float eps_b, float* y, float* save_mean_a,
+                                           float* save_invstd_a, float* save_mean_b, float* save_invstd_b, int64_t rows,
+                                           int32_t C, const float* parts_a, int32_t nparts_a, const float* parts_b,
+                                           int32_t nparts_b, void* workspace, size_t workspace_bytes, uint32_t* y_absmax,
+                                           uint32_t* relu_bits, void* stream) {
+  EVK_REQUIRE(za && zb && y && save_mean_a && save_invstd_a && save_mean_b && save_invstd_b && parts_a && parts_b &&
+                  nparts_a > 0 && nparts_b > 0 && relu_bits,
+              EVK_E_INVALID, "bn_fwd_train_parts_dual: bad argument");
+  int rc = bn_check("bn_fwd_train_parts_dual", rows, C, workspace, workspace_bytes, 2 * BnWorkspace::bytes(C));
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  float* ss_a = BnWorkspace(workspace, C).coef;
+  float* ss_b = BnWorkspace((char*)workspace + BnWorkspace::bytes(C), C).coef;
+  // only the main branch's finalisation owns the slots of y_absmax
+  const int fl = parts_final_lanes(nparts_a);
+  if (fl == parts_final_lanes(nparts_b)) {   // the same form of the merge for both: one launch, a row of workgroups each
+    const BnPartsFinalSet sa = {parts_a, nparts_a, gamma_a, beta_a, running_mean_a, running_var_a, momentum_a, eps_a,
+                                save_mean_a, save_invstd_a, ss_a, y_absmax};
+    const BnPartsFinalSet sb = {parts_b, nparts_b, gamma_b, beta_b, running_mean_b, running_var_b, momentum_b, eps_b,
+                                save_mean_b, save_invstd_b, ss_b, nullptr};
+#define EVK_PARTS_FINAL_DUAL(FC, FL)                                                                                       \
+  hipLaunchKernelGGL((bn_parts_final_dual_kernel<FC, FL>), dim3((C + FC - 1) / FC, 2), dim3(256), 0, st, sa, sb, C, (double)rows)
+    if (fl == 256) EVK_PARTS_FINAL_DUAL(1, 256);
+    else if (fl == 128) EVK_PARTS_FINAL_DUAL(2, 128);
+    else EVK_PARTS_FINAL_DUAL(8, 32);
+#undef EVK_PARTS_FINAL_DUAL
+    rc = check_launch("bn_parts_final_dual");
+    if (rc) return rc;
+  } else {
+    launch_parts_final(st, parts_b, nparts_b, C, (double)rows, gamma_b, beta_b, running_mean_b, running_var_b, momentum_b,
+                       eps_b, save_mean_b, save_invstd_b, ss_b, nullptr, 0);
+    rc = check_launch("bn_parts_final");
+    if (rc) return rc;
+    launch_parts_final(st, parts_a, nparts_a, C, (double)rows, gamma_a, beta_a, running_mean_a, running_var_a, momentum_a,
+                       eps_a, save_mean_a, save_invstd_a, ss_a, y_absmax, 0);
+    rc = check_launch("bn_parts_final");
+    if (rc) return rc;
+  }
+  const size_t n4 = (size_t)rows * C / 4;
+  hipLaunchKernelGGL(bn_apply_dual_kernel, dim3(oneshot_grid(n4)), dim3(256), 0, st, za, zb, (const float*)ss_a,
+                     (const float*)ss_b, y, n4, C, y_absmax, relu_bits);
+  return check_launch("bn_apply_dual");
+}
+
+// 1 when evk_bn_bwd_dual runs the two-map passes for this pair of flags, 0 when it takes the two-call path (host only)
+extern "C" int evk_bn_bwd_dual_fused(uint32_t flags_a, uint32_t flags_b) {
+  return bn_dual_fused((flags_a & EVK_BN_PACK_DX) != 0, (flags_b & EVK_BN_PACK_DX) != 0) ? 1 : 0;
+}
+
+// dza, dzb, both dgamma / dbeta from dy (masked already if it arrived lazily) and the block's ReLU bits.
+// flags_a / flags_b: EVK_BN_PACK_DX per output (its absmax buffer then arrives zero).
+extern "C" int evk_bn_bwd_dual(const float* dy, const float* za, const float* zb, const float* gamma_a,
+                               const float* save_mean_a, const float* save_invstd_a, const float* gamma_b,
+                               const float* save_mean_b, const float* save_invstd_b, float* dza, float* dzb, float* dgamma_a,
+                               float* dbeta_a, float* dgamma_b, float* dbeta_b, int64_t rows, int32_t C, uint32_t flags_a,
+                               uint32_t flags_b, void* workspace, size_t workspace_bytes, uint32_t* dza_absmax,
+                               uint32_t* dzb_absmax, const uint32_t* relu_bits, void* stream) {
+  EVK_REQUIRE(dy && za && zb && save_mean_a && save_invstd_a && save_mean_b && save_invstd_b && dza && dzb && relu_bits,
+              EVK_E_INVALID, "bn_bwd_dual: null pointer");
+  int rc = bn_check("bn_bwd_dual", rows, C, workspace, workspace_bytes, 2 * BnWorkspace::bytes(C));
+  if (rc) return rc;
+  const bool pack_a = (flags_a & EVK_BN_PACK_DX) != 0, pack_b = (flags_b & EVK_BN_PACK_DX) != 0;
+  EVK_REQUIRE((!pack_a || dza_absmax) && (!pack_b || dzb_absmax), EVK_E_INVALID,
+              "bn_bwd_dual: EVK_BN_PACK_DX needs the output's absmax buffer (slots zero on entry)");
+  if (!bn_dual_fused(pack_a, pack_b)) {
+    // a form that was not built: the block-end BatchNorm, then the shortcut's, as their own callers run them
+    rc = evk_bn_bwd_bits(dy, za, nullptr, gamma_a, nullptr, save_mean_a, save_invstd_a, dza, nullptr, dgamma_a, dbeta_a, rows, C,
+                         EVK_BN_RELU | (flags_a & EVK_BN_PACK_DX), 1, workspace, workspace_bytes, dza_absmax, relu_bits, stream);
+    if (rc) return rc;
+    return evk_bn_bwd_bits(dy, zb, nullptr, gamma_b, nullptr, save_mean_b, save_invstd_b, dzb, nullptr, dgamma_b, dbeta_b, rows,
+                           C, flags_b & EVK_BN_PACK_DX, 1, workspace, workspace_bytes, dzb_absmax, relu_bits, stream);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const BnPlan pl = bn_plan(rows, C);
+  const BnWorkspace wa(workspace, C), wb((char*)workspace + BnWorkspace::bytes(C), C);
+  const bool pack = pack_a || pack_b;
+  EVK_BN_LAUNCH_PK(bn_bwd_partial_dual_kernel, pack, dim3(pl.nblk), 0, st, dy, za, zb, save_mean_a, save_invstd_a, save_mean_b,
+                   save_invstd_b, wa.partial, wb.partial, rows, C, pl.rows_per_blk, pl.tpc, pl.rl, pack ? wa.pmax : nullptr,
+                   pack ? wb.pmax : nullptr, relu_bits);
+  rc = check_launch("bn_bwd_partial_dual");
+  if (rc) return rc;
+  const BnBwdFinalSet fa = {wa.partial, gamma_a, save_invstd_a, dgamma_a, dbeta_a, wa.coef, dza_absmax, pack_a ? wa.pmax : nullptr};
+  const BnBwdFinalSet fb = {wb.partial, gamma_b, save_invstd_b, dgamma_b, dbeta_b, wb.coef, dzb_absmax, pack_b ? wb.pmax : nullptr};
+  hipLaunchKernelGGL(bn_bwd_final_dual_kernel, dim3((C + kFinCh - 1) / kFinCh, 2), dim3(256), 0, st, fa, fb, pl.nblk, C,
+                     1.0 / (double)rows);
+  rc = check_launch("bn_bwd_final_dual");
+  if (rc) return rc;
+  const size_t n4 = (size_t)rows * C / 4;
+#define EVK_BN_APPLY_DUAL(PA, PB)                                                                                            \
+  hipLaunchKernelGGL((bn_bwd_apply_dual_kernel<PA, PB>), dim3(oneshot_grid(n4)), dim3(256), 0, st, dy, za, zb, save_mean_a,    \
+                     save_invstd_a, (const float*)wa.coef, save_mean_b, save_invstd_b, (const float*)wb.coef, dza, dzb, n4, C, \
+                     dza_absmax, dzb_absmax, relu_bits)
+  if (pack_a) EVK_BN_APPLY_DUAL(true, true);
+  else if (pack_b) EVK_BN_APPLY_DUAL(false, true);
+  else EVK_BN_APPLY_DUAL(false, false);
+#undef EVK_BN_APPLY_DUAL
+  return check_launch("bn_bwd_apply_dual");
 }
 
 // ---- BatchNorm around a fused consumer (FS-Relation, pointwise.hip: relation_bn_*): the statistics records of the

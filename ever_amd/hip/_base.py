@@ -197,7 +197,8 @@ def _is_packed(t):
 # it) and is masked by its consumer: the block input's data-gradient launch while it adds, or the shortcut's BatchNorm.
 _RELU_BITS = os.environ.get('EVK_RELU_BITS', '1') != '0'
 _LAZY_RES = os.environ.get('EVK_LAZY_RES', '1') != '0'
-relu_bits_stats = {'forward': 0, 'lazy': 0, 'masked_dgrad': 0, 'masked_bn': 0, 'materialized': 0}   # tests / tools
+# ('dual': block ends that ran both of their BatchNorms in the two-map passes, hip/norm.py: batch_norm_act_dual)
+relu_bits_stats = {'forward': 0, 'lazy': 0, 'masked_dgrad': 0, 'masked_bn': 0, 'materialized': 0, 'dual': 0}   # tests / tools
 
 
 def _lazy_bits(t):

@@ -51,3 +51,11 @@ class _Facade(types.ModuleType):
 
 
 sys.modules[__name__].__class__ = _Facade
+
+
+def set_bn_dual(on):
+    """EVK_BN_DUAL: the two BatchNorms at the end of a residual block with a shortcut convolution in passes that take both
+    maps (norm.py: batch_norm_act_dual).  Returns the previous setting."""
+    me = sys.modules[__name__]
+    prev, me._BN_DUAL = me._BN_DUAL, bool(on)
+    return prev

@@ -13,8 +13,8 @@ from . import timing, weight_planes
 from .workspace import workspace
 from ._base import (  # noqa: F401
     HipPathError, _AMAX_HANDOFF, _LAZY_RES, _PACKED, _RELU_BITS, _amax_out, _amax_zeroed, _f16x2, _inherit_amax,
-    _lazy_bits, _mark_packed, _note_amax, _ptr, _require_cuda, _stream, _timed_call, as_nhwc, empty_nhwc, materialize_lazy,
-    observers_active, relu_bits_stats,
+    _lazy_bits, _mark_packed, _note_amax, _ptr, _require_cuda, _stream, _timed_call, as_nhwc, empty_nhwc, is_nhwc,
+    materialize_lazy, observers_active, relu_bits_stats,
 )
 
 
@@ -165,6 +165,127 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, training, momentu
             _mark_packed(y, abits)
         elif abits is not None:
             _note_amax(y, abits)
+        _AMAX_HANDOFF[0] = None
+    return y
+
+
+# The end of a residual block whose shortcut is a convolution: both BatchNorms in passes that take both maps (EVK_BN_DUAL=0:
+# the shortcut's BatchNorm as a layer of its own and the block-end pass with its result as the residual)
+_BN_DUAL = os.environ.get('EVK_BN_DUAL', '1') != '0'
+
+
+def bn_dual_enabled():
+    """the switch, and the ReLU bits with the lazy shortcut gradient the two-map backward stands on"""
+    return _BN_DUAL and _RELU_BITS and _LAZY_RES
+
+
+class _BatchNormDualFn(Function):
+    """relu(bn_a(za) + bn_b(zb)) — the last BatchNorm of a residual block and the BatchNorm of its shortcut convolution
+    (reference ever/module/_resnets.py:108-112 with `downsample`) — without storing bn_b(zb) or reading dy and the ReLU
+    bits twice in the backward (csrc/bn.hip: bn_apply_dual_kernel, bn_bwd_partial_dual_kernel, bn_bwd_apply_dual_kernel).
+    Training mode, both statistics from the convolutions' epilogue records.  The same bits as _BatchNormActFn twice."""
+
+    @staticmethod
+    def forward(ctx, za, zb, weight_a, bias_a, rm_a, rv_a, momentum_a, eps_a, weight_b, bias_b, rm_b, rv_b, momentum_b,
+                eps_b, parts_a, parts_b):
+        n, c, h, w = za.shape
+        rows = n * h * w
+        dev = za.device
+        st = _stream()
+        lib = _C.load()
+        ws_bytes = 2 * lib.evk_bn_workspace_bytes(rows, c)
+        ws = workspace(dev, ws_bytes)
+        y = empty_nhwc(n, c, h, w, dev)
+        saves = [torch.empty((c,), device=dev, dtype=torch.float32) for _ in range(4)]
+        abits = _amax_out(dev)
+        rbits = torch.empty((lib.evk_relu_bits_bytes(za.numel()) // 4,), device=dev, dtype=torch.int32)
+        relu_bits_stats['forward'] += 1
+        relu_bits_stats['dual'] += 1
+        # algorithmic bytes (fp32): read both maps, write y
+        _timed_call('bn', 4.0 * za.numel() * 3, 'evk_bn_fwd_train_parts_dual', za.data_ptr(), zb.data_ptr(), _ptr(weight_a),
+                    _ptr(bias_a), _ptr(rm_a), _ptr(rv_a), float(momentum_a), float(eps_a), _ptr(weight_b), _ptr(bias_b),
+                    _ptr(rm_b), _ptr(rv_b), float(momentum_b), float(eps_b), y.data_ptr(), saves[0].data_ptr(),
+                    saves[1].data_ptr(), saves[2].data_ptr(), saves[3].data_ptr(), rows, c, parts_a[0].data_ptr(), parts_a[1],
+                    parts_b[0].data_ptr(), parts_b[1], ws.data_ptr(), ws_bytes, _ptr(abits), rbits.data_ptr(), st)
+        _AMAX_HANDOFF[0] = (abits, False)
+        ctx.pack_dx = tuple(bool(len(p) > 2 and p[2]) for p in (parts_a, parts_b))
+        ctx.save_for_backward(za, zb, weight_a, weight_b, *saves, rbits)
+        ctx.mark_non_differentiable(*[t for t in (rm_a, rv_a, rm_b, rv_b) if t is not None])
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        za, zb, weight_a, weight_b, mean_a, invstd_a, mean_b, invstd_b, rbits = ctx.saved_tensors
+        n, c, h, w = za.shape
+        rows = n * h * w
+        dev = za.device
+        st = _stream()
+        dy = as_nhwc(materialize_lazy(dy), 'batch_norm.backward')   # an incoming mask is applied before the block's own
+        lib = _C.load()
+        ws_bytes = 2 * lib.evk_bn_workspace_bytes(rows, c)
+        ws = workspace(dev, ws_bytes)
+        dza, dzb = torch.empty_like(za), torch.empty_like(zb)
+
+        def affine_grads(weight):
+            if weight is None:
+                return None, None
+            return (torch.empty((c,), device=dev, dtype=torch.float32), torch.empty((c,), device=dev, dtype=torch.float32))
+        dgamma_a, dbeta_a = affine_grads(weight_a)
+        dgamma_b, dbeta_b = affine_grads(weight_b)
+        # each output is its producing convolution's dy and nothing else where that convolution said so (EVK_BN_PACK_DX)
+        packs, scales = [], []
+        for want in ctx.pack_dx:
+            pack = want and _f16x2()
+            abits = _amax_zeroed(dev) if pack else _amax_out(dev)
+            packs.append(bool(pack and abits is not None))
+            scales.append(abits)
+        # reduce pass reads dy and both maps; apply pass reads them again and writes both gradients
+        relu_bits_stats['lazy'] += 1          # the shortcut's share of dy is never written masked ...
+        relu_bits_stats['masked_bn'] += 1     # ... its BatchNorm masks it in the pass it shares with the block's last one
+        _timed_call('bn', 4.0 * za.numel() * 8, 'evk_bn_bwd_dual', dy.data_ptr(), za.data_ptr(), zb.data_ptr(), _ptr(weight_a),
+                    mean_a.data_ptr(), invstd_a.data_ptr(), _ptr(weight_b), mean_b.data_ptr(), invstd_b.data_ptr(),
+                    dza.data_ptr(), dzb.data_ptr(), _ptr(dgamma_a), _ptr(dbeta_a), _ptr(dgamma_b), _ptr(dbeta_b), rows, c,
+                    2 if packs[0] else 0, 2 if packs[1] else 0, ws.data_ptr(), ws_bytes, _ptr(scales[0]), _ptr(scales[1]),
+                    rbits.data_ptr(), st)
+        for dz, pack, abits in ((dza, packs[0], scales[0]), (dzb, packs[1], scales[1])):
+            if pack:
+                _mark_packed(dz, abits)
+            elif abits is not None:
+                _note_amax(dz, abits)
+        need = ctx.needs_input_grad
+        return (dza, dzb, dgamma_a if need[2] else None, dbeta_a if need[3] else None, None, None, None, None,
+                dgamma_b if need[8] else None, dbeta_b if need[9] else None, None, None, None, None, None, None)
+
+
+def batch_norm_act_dual(za, bn_a, zb, bn_b):
+    """relu(bn_a(za) + bn_b(zb)) for the two BatchNorm2d modules at the end of a residual block with a shortcut convolution,
+    or None where the two-map passes do not apply and the caller runs the layers one by one: both maps must carry their
+    convolutions' statistics records, both modules must be in training mode with batch statistics, and the block's
+    gradients must be wanted (the backward writes both)."""
+    pa, pb = getattr(za, '_evk_bn_parts', None), getattr(zb, '_evk_bn_parts', None)
+    if (not (_BN_DUAL and _RELU_BITS and _LAZY_RES) or pa is None or pb is None or pa[1] <= 0 or pb[1] <= 0
+            or za.shape != zb.shape or za.shape[1] % 4 or not (torch.is_grad_enabled() and za.requires_grad and zb.requires_grad)
+            or not (is_nhwc(za) and is_nhwc(zb)) or observers_active()):
+        return None
+    for bn in (bn_a, bn_b):
+        if not bn.training or bn.momentum is None or za.shape[0] * za.shape[2] * za.shape[3] == 1:
+            return None
+    del za._evk_bn_parts, zb._evk_bn_parts
+    args = []
+    for bn in (bn_b, bn_a):     # (the shortcut's bookkeeping first, as its own layer call would have come first)
+        if bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn._nbt_pending = getattr(bn, '_nbt_pending', 0) + 1
+        track = bn.track_running_stats
+        if track and bn.running_mean is not None:
+            weight_planes.note_running_stats_changed()
+        args.append((bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
+                     bn.momentum, bn.eps))
+    _AMAX_HANDOFF[0] = None
+    y = _BatchNormDualFn.apply(za, zb, *args[1], *args[0], pa, pb)
+    if _AMAX_HANDOFF[0] is not None:
+        if _AMAX_HANDOFF[0][0] is not None:
+            _note_amax(y, _AMAX_HANDOFF[0][0])
         _AMAX_HANDOFF[0] = None
     return y
 

@@ -60,14 +60,41 @@ def _inference(bn):
     return (not bn.training) and not torch.is_grad_enabled()
 
 
-def _fork(block, x):
+def _fork(block, x, raw_shortcut=False):
     """(conv1(x), shortcut) — the block input feeds both; one autograd node so that the two input
-    gradients are summed inside the data-gradient kernel (hip/conv.py:_ConvForkFn)."""
+    gradients are summed inside the data-gradient kernel (hip/conv.py:_ConvForkFn).
+    raw_shortcut: hand back the shortcut convolution's output WITHOUT its BatchNorm (_block_end runs it)."""
     if block.downsample is None:
         return HF.conv2d_fork(x, block.conv1, bn_stats=(_takes_epilogue_stats(block.bn1), False))
     h, s = HF.conv2d_fork(x, block.conv1, block.downsample[0],
                           bn_stats=(_takes_epilogue_stats(block.bn1), _takes_epilogue_stats(block.downsample[1])))
-    return h, block.downsample[1](s)
+    return h, (s if raw_shortcut else block.downsample[1](s))
+
+
+def _dual_ok(block, conv, bn):
+    """May the block's last BatchNorm and its shortcut convolution's BatchNorm run in passes that take both maps
+    (hip/norm.py: batch_norm_act_dual, EVK_BN_DUAL)?  Training with batch statistics from the convolution epilogues, both
+    norms this package's plain BatchNorm2d, the lazy shortcut gradient allowed (_lazy_ok), nobody watching: the shortcut's
+    normalised map, which a hook would be handed, is never stored."""
+    ds = block.downsample
+    if ds is None or not HF.bn_dual_enabled() or not _lazy_ok(block, bn) or _use_folded(conv, bn):
+        return False
+    if not (_takes_epilogue_stats(bn) and _takes_epilogue_stats(ds[1]) and bn.training and ds[1].training):
+        return False
+    return not any(m._backward_hooks or m._backward_pre_hooks or m._forward_pre_hooks for m in (bn, ds[1]))
+
+
+def _block_end(block, conv, bn, out, s, dual):
+    """relu(bn(conv(out)) + shortcut).  dual (_dual_ok): s is the shortcut convolution's raw output and both BatchNorms run in
+    the two-map passes; where those cannot take the pair after all (a map too small for its convolution to leave statistics
+    records), the shortcut's BatchNorm runs here as the layer it is."""
+    if dual:
+        z = conv(out, bn_stats=True)
+        y = HF.batch_norm_act_dual(z, bn, s, block.downsample[1])
+        if y is not None:
+            return y
+        return bn(z, residual=block.downsample[1](s), relu=True, lazy_res=True)   # (z still carries its records, if any)
+    return conv_bn(conv, bn, out, residual=s, relu=True, lazy_res=_lazy_ok(block, bn))
 
 
 def _lazy_ok(block, bn):
@@ -117,10 +144,11 @@ class BasicBlock(nn.Module):
             shortcut = x if self.downsample is None else conv_bn(self.downsample[0], self.downsample[1], x)
             out = conv_bn(self.conv1, self.bn1, x, relu=True)
             return conv_bn(self.conv2, self.bn2, out, residual=shortcut, relu=True)
-        h, shortcut = _fork(self, x)
+        dual = _dual_ok(self, self.conv2, self.bn2)
+        h, shortcut = _fork(self, x, raw_shortcut=dual)
         out = self.bn1(h, relu=True, conv_only=True)       # read by conv2 alone
         # (the shortcut's gradient reaches only the fork node or the down-sampling BatchNorm: lazy_res)
-        return conv_bn(self.conv2, self.bn2, out, residual=shortcut, relu=True, lazy_res=_lazy_ok(self, self.bn2))
+        return _block_end(self, self.conv2, self.bn2, out, shortcut, dual)
 
 
 class Bottleneck(nn.Module):
@@ -152,10 +180,11 @@ class Bottleneck(nn.Module):
             out = conv_bn(self.conv1, self.bn1, x, relu=True)
             out = conv_bn(self.conv2, self.bn2, out, relu=True)
             return conv_bn(self.conv3, self.bn3, out, residual=shortcut, relu=True)
-        h, shortcut = _fork(self, x)
+        dual = _dual_ok(self, self.conv3, self.bn3)
+        h, shortcut = _fork(self, x, raw_shortcut=dual)
         out = self.bn1(h, relu=True, conv_only=True)       # read by conv2 alone
         out = conv_bn(self.conv2, self.bn2, out, relu=True, conv_only=True)   # ... and this by conv3 alone
-        return conv_bn(self.conv3, self.bn3, out, residual=shortcut, relu=True, lazy_res=_lazy_ok(self, self.bn3))
+        return _block_end(self, self.conv3, self.bn3, out, shortcut, dual)
 
 
 class ResNet(nn.Module):

@@ -390,6 +390,30 @@ int evk_bn_bwd_bits(const float* dy, const float* x, const float* y, const float
                     float* dgamma, float* dbeta, int64_t rows, int32_t C, uint32_t flags, int32_t train,
                     void* workspace, size_t workspace_bytes, uint32_t* dx_absmax, const uint32_t* relu_bits, void* stream);
 
+/* Both BatchNorms at the end of a residual block whose shortcut is a convolution (reference _resnets.py:108-112 with
+ * `downsample`): y = relu(bn_a(za) + bn_b(zb)), za the main branch's last convolution output, zb the shortcut convolution's,
+ * in passes that take both maps — bn_b(zb) is never stored.  Training mode, both statistics from epilogue records (as
+ * evk_bn_fwd_train_parts).  Every output has the bits of evk_bn_fwd_train_parts on zb followed by
+ * evk_bn_fwd_train_parts_bits on za with that result as the residual, and of evk_bn_bwd_bits on each map in the backward.
+ * workspace: 2 * evk_bn_workspace_bytes(rows, C).  y_absmax as in evk_bn_fwd_train_parts (optional); relu_bits required. */
+int evk_bn_fwd_train_parts_dual(const float* za, const float* zb, const float* gamma_a, const float* beta_a,
+                                float* running_mean_a, float* running_var_a, float momentum_a, float eps_a,
+                                const float* gamma_b, const float* beta_b, float* running_mean_b, float* running_var_b,
+                                float momentum_b, float eps_b, float* y, float* save_mean_a, float* save_invstd_a,
+                                float* save_mean_b, float* save_invstd_b, int64_t rows, int32_t C, const float* parts_a,
+                                int32_t nparts_a, const float* parts_b, int32_t nparts_b, void* workspace,
+                                size_t workspace_bytes, uint32_t* y_absmax, uint32_t* relu_bits, void* stream);
+/* The backward of the pair: dy is the gradient of y (masked already if it arrived with bits of its own), relu_bits the
+ * forward's.  flags_a / flags_b: EVK_BN_PACK_DX for that output (its absmax buffer then arrives zero), nothing else.
+ * evk_bn_bwd_dual_fused (host only) tells whether a pair of flags runs the two-map passes (1) or, a form that was not
+ * built, the two evk_bn_bwd_bits calls inside the entry point (0); the results are the same bits either way. */
+int evk_bn_bwd_dual(const float* dy, const float* za, const float* zb, const float* gamma_a, const float* save_mean_a,
+                    const float* save_invstd_a, const float* gamma_b, const float* save_mean_b, const float* save_invstd_b,
+                    float* dza, float* dzb, float* dgamma_a, float* dbeta_a, float* dgamma_b, float* dbeta_b, int64_t rows,
+                    int32_t C, uint32_t flags_a, uint32_t flags_b, void* workspace, size_t workspace_bytes,
+                    uint32_t* dza_absmax, uint32_t* dzb_absmax, const uint32_t* relu_bits, void* stream);
+int evk_bn_bwd_dual_fused(uint32_t flags_a, uint32_t flags_b);
+
 /* `to` waits for everything enqueued on `from` so far (an event of a per-device ring recorded on `from`, waited for on
  * `to`): the fork of the weight-gradient side stream from the backward's stream, once per convolution layer
  * (ever_amd/hip/functional.py).  Not thread-safe per device (the backward of one device runs on one thread).
