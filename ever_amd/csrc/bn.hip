@@ -112,11 +112,16 @@ __device__ __forceinline__ int chunk_of(size_t blk_base, int c4) {
 // per workgroup would cost more than the 4 KB a workgroup streams.
 // PK: y is written as packed words of y / s (x3_common.hpp: pack_hl), s from the bound the finalisation left in slot 0
 // of `amax` — the tensor is the next convolution's operand and nothing else.
-template <bool PK = false>
+// DUAL (the end of a residual block whose shortcut is a convolution, see evk_bn_fwd_train_parts_dual below): `residual` is
+// the shortcut convolution's output zb and the added term is bn_b(zb) = zb*scb + shb, computed in registers from
+// `scale_shift_b` — an expression of its own, so it is rounded as the stored copy was (one fused multiply-add) before the
+// add; always with ReLU and bits.
+template <bool PK, bool DUAL>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ residual,
-                                                       const float* __restrict__ scale_shift, float* __restrict__ y,
+                                                       const float* __restrict__ scale_shift,
+                                                       const float* __restrict__ scale_shift_b, float* __restrict__ y,
                                                        size_t n4, int C, int relu, uint32_t* __restrict__ amax,
-                                                       uint32_t* __restrict__ relu_bits = nullptr) {
+                                                       uint32_t* __restrict__ relu_bits) {
   const size_t base = (size_t)bn_blk() * 256;
   const size_t i = base + threadIdx.x;
   const bool valid = i < n4;
@@ -128,14 +133,22 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     const int cb = chunk_of(base, c4);
     const f32x4 sc = reinterpret_cast<const f32x4*>(scale_shift)[cb];
     const f32x4 sh = reinterpret_cast<const f32x4*>(scale_shift + C)[cb];
+    f32x4 yb = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (DUAL) {
+      const f32x4 scb = reinterpret_cast<const f32x4*>(scale_shift_b)[cb];
+      const f32x4 shb = reinterpret_cast<const f32x4*>(scale_shift_b + C)[cb];
+      yb = bn_ld(residual, i) * scb + shb;
+    }
     v = bn_ld(x, i) * sc + sh;
-    if (residual) v += bn_ld(residual, i);
+    if constexpr (DUAL) v += yb;
+    else if (residual) v += bn_ld(residual, i);
   }
   // the backward's mask, one bit per element (common.hpp: relu_bits_*): every lane of the wave takes part (v = 0 where
-  // the element does not exist), i >> 6 is this wave's chunk
-  if (relu_bits) relu_bits_store(relu_bits, i >> 6, v.x > 0.f, v.y > 0.f, v.z > 0.f, v.w > 0.f);
+  // the element does not exist), i >> 6 is this wave's chunk; a wave wholly past the end has no chunk in the buffer
+  if ((DUAL || relu_bits) && ((i >> 6) << 6) < n4)
+    relu_bits_store(relu_bits, i >> 6, v.x > 0.f, v.y > 0.f, v.z > 0.f, v.w > 0.f);
   if (valid) {
-    if (relu) {
+    if (DUAL || relu) {
       v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
     }
     if constexpr (PK) {
@@ -150,118 +163,124 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 
 // Backward stage 1: g = dy * (y > 0) ; partial[blk][0][C] = sum g, [1][C] = sum g * xhat.
 // Optionally writes g to d_residual.
-// PK (dx will be written packed, EVK_BN_PACK_DX): also pmax[blk][0][C] = max |g|, [1][C] = max |xhat| — what the
-// finalisation needs to bound |dx| per channel BEFORE the apply pass writes it under that scale.
+// NM = 2 (the two BatchNorms at the end of a residual block whose shortcut is a convolution, evk_bn_bwd_dual): g is read and
+// masked ONCE — mask mode 3, no d_residual — and summed against both maps, xhat of `x` into `partial`, xhat of `xb` (under
+// mean_b / invstd_b) into `partial_b`: one plan, row order and fold, so each record has the bits the NM = 1 pass gives.
+// PK (dx will be written packed, EVK_BN_PACK_DX): also pmax[blk][0][C] = max |g|, [1][C] = max |xhat| (and pmax_b) — what
+// the finalisation needs to bound |dx| per channel BEFORE the apply pass writes it under that scale.
 // (plain loads: the apply pass re-reads what this pass streams.  The non-temporal hint here, gated by map size, measured
 // level from 128 MB up and -0.3 % below — removed)
 __device__ __forceinline__ f32x4 bp_ld(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-template <bool PK>
-__global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                             const float* __restrict__ y,
-                                                             const float* __restrict__ mean,
-                                                             const float* __restrict__ invstd,
-                                                             const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta,
-                                                             float* __restrict__ d_residual,
-                                                             float* __restrict__ partial, int64_t rows, int C,
-                                                             int64_t rows_per_blk, int tpc, int rl, int relu,
-                                                             float* __restrict__ pmax,
-                                                             const uint32_t* __restrict__ bits = nullptr) {
+template <int NM, bool PK>
+__global__ __launch_bounds__(256) void bn_bwd_partial_kernel(
+    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ xb, const float* __restrict__ y,
+    const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ mean_b,
+    const float* __restrict__ invstd_b, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ d_residual, float* __restrict__ partial, float* __restrict__ partial_b, int64_t rows, int C,
+    int64_t rows_per_blk, int tpc, int rl, int relu, float* __restrict__ pmax, float* __restrict__ pmax_b,
+    const uint32_t* __restrict__ bits) {
   // relu: 0 none, 1 mask from the saved output y, 2 mask recomputed from x (no residual: the
   // forward's pre-activation is x*sc+sh with the same sc/sh arithmetic as bn_stats_final_kernel), 3 mask from `bits`
   // (common.hpp: relu_bits_*: the forward's own bits, or the mask of a gradient that arrives unmasked — EVK_BN_LAZY_RES)
+  if constexpr (NM == 2) {
+    relu = 3;
+    d_residual = nullptr;
+  }
   __shared__ f32x4 red[2][256];
+  const float* const xs[2] = {x, xb};
+  const float* const means[2] = {mean, mean_b};
+  const float* const invstds[2] = {invstd, invstd_b};
+  float* const partials[2] = {partial, partial_b};
+  float* const pmaxs[2] = {pmax, pmax_b};
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const int c4 = C >> 2;
   const int tc = threadIdx.x % tpc, tr = threadIdx.x / tpc;
   const int64_t r0 = (int64_t)bn_blk() * rows_per_blk;
   const int64_t r1 = min(rows, r0 + rows_per_blk);
   for (int cb = tc; cb < c4; cb += tpc) {
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + cb * 4);
-    const f32x4 is = *reinterpret_cast<const f32x4*>(invstd + cb * 4);
-    f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-    if (relu == 2) {
-      const f32x4 one = {1.f, 1.f, 1.f, 1.f}, zero = {0.f, 0.f, 0.f, 0.f};
-      const f32x4 g4 = gamma ? *reinterpret_cast<const f32x4*>(gamma + cb * 4) : one;
-      const f32x4 b4 = beta ? *reinterpret_cast<const f32x4*>(beta + cb * 4) : zero;
-      sc = g4 * is;
-      sh = b4 - mu * sc;
+    f32x4 mu[NM], is[NM], q[NM], xm[NM];
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+      mu[m] = *reinterpret_cast<const f32x4*>(means[m] + cb * 4);
+      is[m] = *reinterpret_cast<const f32x4*>(invstds[m] + cb * 4);
+      q[m] = xm[m] = zero4;
     }
-    f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
-    f32x4 gm = {0.f, 0.f, 0.f, 0.f}, xm = {0.f, 0.f, 0.f, 0.f};
+    f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = zero4;
+    if (relu == 2) {
+      const f32x4 one = {1.f, 1.f, 1.f, 1.f};
+      const f32x4 g4 = gamma ? *reinterpret_cast<const f32x4*>(gamma + cb * 4) : one;
+      const f32x4 b4 = beta ? *reinterpret_cast<const f32x4*>(beta + cb * 4) : zero4;
+      sc = g4 * is[0];
+      sh = b4 - mu[0] * sc;
+    }
+    f32x4 s = zero4, gm = zero4;
     if (tr < rl) {
-      auto one = [&](const f32x4 gin, const f32x4 xv, const f32x4 yin, size_t off) {
+      auto one = [&](const f32x4 gin, const f32x4* xv, const f32x4 yin, size_t off) {
         f32x4 g = gin;
         if (relu == 3) {
           g = relu_bits_mask(g, bits, off >> 2);
         } else if (relu) {
-          const f32x4 yy = (relu == 1) ? yin : xv * sc + sh;
+          const f32x4 yy = (relu == 1) ? yin : xv[0] * sc + sh;
           g = relu_mask(g, yy);
         }
         if (d_residual) *reinterpret_cast<f32x4*>(d_residual + off) = g;
         s += g;
-        const f32x4 xh = (xv - mu) * is;
-        q += g * xh;
+        f32x4 xh[NM];
+#pragma unroll
+        for (int m = 0; m < NM; ++m) {
+          xh[m] = (xv[m] - mu[m]) * is[m];
+          q[m] += g * xh[m];
+        }
         if constexpr (PK) {
-          gm.x = fmaxf(gm.x, fabsf(g.x)); gm.y = fmaxf(gm.y, fabsf(g.y));
-          gm.z = fmaxf(gm.z, fabsf(g.z)); gm.w = fmaxf(gm.w, fabsf(g.w));
-          xm.x = fmaxf(xm.x, fabsf(xh.x)); xm.y = fmaxf(xm.y, fabsf(xh.y));
-          xm.z = fmaxf(xm.z, fabsf(xh.z)); xm.w = fmaxf(xm.w, fabsf(xh.w));
+          absmax4(gm, g);
+#pragma unroll
+          for (int m = 0; m < NM; ++m) absmax4(xm[m], xh[m]);
         }
       };
-      const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
       int64_t r = r0 + tr;
       const int64_t st = rl;
       // four rows per trip: 8-12 independent 16-byte loads in flight per lane
       for (; r + 3 * st < r1; r += 4 * st) {
-        const size_t o0 = (size_t)r * C + cb * 4, o1 = (size_t)(r + st) * C + cb * 4;
-        const size_t o2 = (size_t)(r + 2 * st) * C + cb * 4, o3 = (size_t)(r + 3 * st) * C + cb * 4;
-        const f32x4 g0 = bp_ld(dy + o0), g1 = bp_ld(dy + o1);
-        const f32x4 g2 = bp_ld(dy + o2), g3 = bp_ld(dy + o3);
-        const f32x4 x0 = bp_ld(x + o0), x1 = bp_ld(x + o1);
-        const f32x4 x2 = bp_ld(x + o2), x3 = bp_ld(x + o3);
-        f32x4 y0 = zero4, y1 = zero4, y2 = zero4, y3 = zero4;
+        size_t o[4];
+        f32x4 g[4], xv[4][NM], yv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = (size_t)(r + k * st) * C + cb * 4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = bp_ld(dy + o[k]);
+#pragma unroll
+        for (int m = 0; m < NM; ++m)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) xv[k][m] = bp_ld(xs[m] + o[k]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) yv[k] = zero4;
         if (relu == 1) {
-          y0 = bp_ld(y + o0);
-          y1 = bp_ld(y + o1);
-          y2 = bp_ld(y + o2);
-          y3 = bp_ld(y + o3);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) yv[k] = bp_ld(y + o[k]);
         }
-        one(g0, x0, y0, o0);
-        one(g1, x1, y1, o1);
-        one(g2, x2, y2, o2);
-        one(g3, x3, y3, o3);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) one(g[k], xv[k], yv[k], o[k]);
       }
       for (; r < r1; r += st) {
         const size_t o0 = (size_t)r * C + cb * 4;
+        f32x4 xv[NM];
         const f32x4 g0 = bp_ld(dy + o0);
-        const f32x4 x0 = bp_ld(x + o0);
-        const f32x4 y0 = (relu == 1) ? bp_ld(y + o0) : zero4;
-        one(g0, x0, y0, o0);
+#pragma unroll
+        for (int m = 0; m < NM; ++m) xv[m] = bp_ld(xs[m] + o0);
+        one(g0, xv, (relu == 1) ? bp_ld(y + o0) : zero4, o0);
       }
     }
-    fold_store_record(red, s, q, partial, bn_blk(), C, cb, tc, tr, tpc, rl);
+#pragma unroll
+    for (int m = 0; m < NM; ++m) fold_store_record(red, s, q[m], partials[m], bn_blk(), C, cb, tc, tr, tpc, rl);
     if constexpr (PK) {
-      red[0][threadIdx.x] = gm;
-      red[1][threadIdx.x] = xm;
-      __syncthreads();
-      if (tr == 0) {
-        for (int k = 1; k < rl; ++k) {
-          const f32x4 a = red[0][k * tpc + tc], b = red[1][k * tpc + tc];
-          gm.x = fmaxf(gm.x, a.x); gm.y = fmaxf(gm.y, a.y); gm.z = fmaxf(gm.z, a.z); gm.w = fmaxf(gm.w, a.w);
-          xm.x = fmaxf(xm.x, b.x); xm.y = fmaxf(xm.y, b.y); xm.z = fmaxf(xm.z, b.z); xm.w = fmaxf(xm.w, b.w);
-        }
-        float* o = pmax + (size_t)bn_blk() * 2 * C;
-        *reinterpret_cast<f32x4*>(o + cb * 4) = gm;
-        *reinterpret_cast<f32x4*>(o + C + cb * 4) = xm;
-      }
-      __syncthreads();
+#pragma unroll
+      for (int m = 0; m < NM; ++m) fold_store_maxima(red, gm, xm[m], pmaxs[m], bn_blk(), C, cb, tc, tr, tpc, rl);
     }
   }
 }
 
 // coef[0][C] = gamma*invstd ; coef[1][C] = mean(g) ; coef[2][C] = mean(g*xhat)  (0 when !train)
 // FC channels x 256 / FC lanes per workgroup: 8 x 32 by default; 2 x 128 (four times the workgroups) when the partials are many
-// (the body is a function of its own so that bn_bwd_final_dual_kernel below can finish two BatchNorms in one launch)
+// (the body: bn_bwd_final_kernel below hands it the arguments of the BatchNorm its row of workgroups finishes)
 template <int FC>
 __device__ __forceinline__ void bn_bwd_final_body(const float* __restrict__ partial, int nblk, int C,
                                                   double inv_rows, const float* __restrict__ gamma,
@@ -320,20 +339,61 @@ __device__ __forceinline__ void bn_bwd_final_body(const float* __restrict__ part
     if (bits) atomicMax(&amax[0], bits);
   }
 }
-template <int FC = kFinCh>
-__global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restrict__ partial, int nblk, int C,
-                                                           double inv_rows, const float* __restrict__ gamma,
-                                                           const float* __restrict__ invstd,
-                                                           float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                           float* __restrict__ coef, int train,
-                                                           uint32_t* __restrict__ amax,
-                                                           const float* __restrict__ pmax) {
-  bn_bwd_final_body<FC>(partial, nblk, C, inv_rows, gamma, invstd, dgamma, dbeta, coef, train, amax, pmax);
+// One BatchNorm's arguments; the kernel takes NR sets, one per row of workgroups (gridDim.y = NR: 1, or 2 for the pair at the
+// end of a residual block whose shortcut is a convolution): blockIdx.y selects the set, the workgroups of a row look at
+// blockIdx.x alone (bn_fin_group, zero_amax).  (NR is a template argument because with two sets in every launch the one-row
+// launches paid for the second: 0.1-0.4 us on launches of 6-17 us, above the parent's range in every run.)
+struct BnBwdFinalSet {
+  const float *partial, *gamma, *invstd;
+  float *dgamma, *dbeta, *coef;
+  int train;
+  uint32_t* amax;
+  const float* pmax;
+};
+template <typename Set, int NR>
+struct BnFinalSets {
+  Set row[NR];
+};
+// the set of this workgroup's row (both sets loaded, then selected — the two-row kernels' form since they exist; loading the
+// one at index blockIdx.y measured the same)
+template <typename Set, int NR>
+__device__ __forceinline__ Set bn_final_row(const BnFinalSets<Set, NR>& sets) {
+  if constexpr (NR == 1) return sets.row[0];
+  else return blockIdx.y ? sets.row[1] : sets.row[0];
+}
+template <int NR>
+__global__ __launch_bounds__(256) void bn_bwd_final_kernel(BnFinalSets<BnBwdFinalSet, NR> sets, int nblk, int C, double inv_rows) {
+  const BnBwdFinalSet s = bn_final_row(sets);
+  bn_bwd_final_body<kFinCh>(s.partial, nblk, C, inv_rows, s.gamma, s.invstd, s.dgamma, s.dbeta, s.coef, s.train, s.amax, s.pmax);
 }
 
 // dx = coef0 * (g - coef1 - xhat*coef2); one 16-byte element per thread (see bn_apply_kernel), the per-channel
 // vectors read through L1.  PK: dx is written as packed words of dx / s (x3_common.hpp: pack_hl), s from the bound the
 // finalisation left in `amax` — the tensor is the producing convolution's dy operand and nothing else.
+// One map's share of an element, in two steps so that a kernel can issue the loads of the channel chunk's coefficients ahead
+// of its streaming loads (in one step the apply kernels came out 2.2-2.5 % slower): bn_dx_coef loads them, bn_dx_store forms
+// dx, stores it packed or plain and returns it for block_absmax.
+struct BnDxCoef {
+  f32x4 k0, k1, k2, mu, is;
+};
+__device__ __forceinline__ BnDxCoef bn_dx_coef(const float* __restrict__ coef, const float* __restrict__ mean,
+                                               const float* __restrict__ invstd, int C, int c) {
+  return {reinterpret_cast<const f32x4*>(coef)[c], reinterpret_cast<const f32x4*>(coef + C)[c],
+          reinterpret_cast<const f32x4*>(coef + 2 * C)[c], reinterpret_cast<const f32x4*>(mean)[c],
+          reinterpret_cast<const f32x4*>(invstd)[c]};
+}
+template <bool PK>
+__device__ __forceinline__ f32x4 bn_dx_store(const BnDxCoef& k, const f32x4 g, const f32x4 xv, float* __restrict__ dx, size_t i,
+                                             float pk_inv) {
+  const f32x4 xh = (xv - k.mu) * k.is;
+  const f32x4 out = k.k0 * (g - k.k1 - xh * k.k2);
+  if constexpr (PK) {
+    reinterpret_cast<u32x4*>(dx)[i] = pack_hl4(out, pk_inv);
+  } else {
+    reinterpret_cast<f32x4*>(dx)[i] = out;
+  }
+  return out;
+}
 template <bool PK>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                            const float* __restrict__ y, const float* __restrict__ mean,
@@ -353,11 +413,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     const int c4 = C >> 2;
     const int c = chunk_of(base, c4);
     const f32x4 one4 = {1.f, 1.f, 1.f, 1.f}, z4 = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 k0 = reinterpret_cast<const f32x4*>(coef)[c];
-    const f32x4 k1 = reinterpret_cast<const f32x4*>(coef + C)[c];
-    const f32x4 k2 = reinterpret_cast<const f32x4*>(coef + 2 * C)[c];
-    const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[c];
-    const f32x4 is = reinterpret_cast<const f32x4*>(invstd)[c];
+    const BnDxCoef k = bn_dx_coef(coef, mean, invstd, C, c);
     f32x4 g = bn_ld(dy, i);
     const f32x4 xv = bn_ld(x, i);
     if (relu == 3) {
@@ -367,19 +423,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
       if (relu == 1) {
         yy = reinterpret_cast<const f32x4*>(y)[i];
       } else {  // the forward's pre-activation, same sc/sh arithmetic as bn_stats_final_kernel
-        const f32x4 sc = (gamma ? reinterpret_cast<const f32x4*>(gamma)[c] : one4) * is;
-        const f32x4 sh = (beta ? reinterpret_cast<const f32x4*>(beta)[c] : z4) - mu * sc;
+        const f32x4 sc = (gamma ? reinterpret_cast<const f32x4*>(gamma)[c] : one4) * k.is;
+        const f32x4 sh = (beta ? reinterpret_cast<const f32x4*>(beta)[c] : z4) - k.mu * sc;
         yy = xv * sc + sh;
       }
       g = relu_mask(g, yy);
     }
-    const f32x4 xh = (xv - mu) * is;
-    out = k0 * (g - k1 - xh * k2);
-    if constexpr (PK) {
-      reinterpret_cast<u32x4*>(dx)[i] = pack_hl4(out, pk_inv);
-    } else {
-      reinterpret_cast<f32x4*>(dx)[i] = out;
-    }
+    out = bn_dx_store<PK>(k, g, xv, dx, i, pk_inv);
   }
   if constexpr (!PK)
     if (amax) block_absmax(out, valid, amax);   // all lanes of the workgroup arrive here together
@@ -390,7 +440,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 // subset each, then the 32 lanes folded in index order — the same outputs as bn_stats_final_kernel, no pass over x.
 // FC channels x FL record lanes per workgroup (FC * FL = 256): 8 x 32 for the small maps; 2 x 128 where a channel has
 // hundreds of records (the 128^2 maps: 2048 per channel — at 32 lanes each lane walked 64 strided records: 9-47 us a launch)
-// (the body is a function of its own so that bn_parts_final_dual_kernel below can merge two BatchNorms' records in one launch)
+// (the body: bn_parts_final_kernel below hands it the arguments of the BatchNorm whose records its row of workgroups merges)
 template <int FC, int FL>
 __device__ __forceinline__ void bn_parts_final_body(const float* __restrict__ parts, int nparts, int C,
                                                     double rows, const float* __restrict__ gamma,
@@ -474,21 +524,8 @@ __device__ __forceinline__ void bn_parts_final_body(const float* __restrict__ pa
     if (bits) atomicMax(&amax[0], bits);   // slot 0 alone: the apply pass reads one word (see bn_bwd_final_kernel)
   }
 }
-template <int FC, int FL>
-__global__ __launch_bounds__(256) void bn_parts_final_kernel(const float* __restrict__ parts, int nparts, int C,
-                                                             double rows, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta,
-                                                             float* __restrict__ running_mean,
-                                                             float* __restrict__ running_var, float momentum, float eps,
-                                                             float* __restrict__ save_mean, float* __restrict__ save_invstd,
-                                                             float* __restrict__ scale_shift,
-                                                             uint32_t* __restrict__ amax, int pack) {
-  bn_parts_final_body<FC, FL>(parts, nparts, C, rows, gamma, beta, running_mean, running_var, momentum, eps, save_mean,
-                              save_invstd, scale_shift, amax, pack);
-}
-
-// The two finalisations of a block end with a shortcut convolution in ONE launch each: blockIdx.y selects the BatchNorm, the
-// workgroups of a row do what the single kernels' workgroups do (bn_fin_group and zero_amax look at blockIdx.x alone).
+// One BatchNorm's arguments, NR sets, one per row of workgroups as for bn_bwd_final_kernel (two rows: the two merges of a
+// block end with a shortcut convolution in ONE launch, when both take the same form FC x FL).
 struct BnPartsFinalSet {
   const float* parts;
   int nparts;
@@ -497,23 +534,14 @@ struct BnPartsFinalSet {
   float momentum, eps;
   float *save_mean, *save_invstd, *scale_shift;
   uint32_t* amax;
+  int pack;
 };
-template <int FC, int FL>
-__global__ __launch_bounds__(256) void bn_parts_final_dual_kernel(BnPartsFinalSet a, BnPartsFinalSet b, int C, double rows) {
-  const BnPartsFinalSet s = blockIdx.y ? b : a;
+template <int FC, int FL, int NR>
+__global__ __launch_bounds__(256) void bn_parts_final_kernel(BnFinalSets<BnPartsFinalSet, NR> sets, int C, double rows) {
+  const BnPartsFinalSet s = bn_final_row(sets);
+  // (a pair never packs — the output of a block end has several readers — so its kernels carry no code or LDS for the bound)
   bn_parts_final_body<FC, FL>(s.parts, s.nparts, C, rows, s.gamma, s.beta, s.running_mean, s.running_var, s.momentum, s.eps,
-                              s.save_mean, s.save_invstd, s.scale_shift, s.amax, 0);
-}
-struct BnBwdFinalSet {
-  const float *partial, *gamma, *invstd;
-  float *dgamma, *dbeta, *coef;
-  uint32_t* amax;
-  const float* pmax;
-};
-__global__ __launch_bounds__(256) void bn_bwd_final_dual_kernel(BnBwdFinalSet a, BnBwdFinalSet b, int nblk, int C,
-                                                                double inv_rows) {
-  const BnBwdFinalSet s = blockIdx.y ? b : a;
-  bn_bwd_final_body<kFinCh>(s.partial, nblk, C, inv_rows, s.gamma, s.invstd, s.dgamma, s.dbeta, s.coef, 1, s.amax, s.pmax);
+                              s.save_mean, s.save_invstd, s.scale_shift, s.amax, NR == 1 ? s.pack : 0);
 }
 
 // (A one-launch backward for small maps — every thread's rows in registers across two grid-wide barriers, 3 tensor transfers
@@ -525,168 +553,81 @@ __global__ __launch_bounds__(256) void bn_bwd_final_dual_kernel(BnBwdFinalSet a,
 // record lanes per channel of the merge: bn_parts_final_kernel<256 / lanes, lanes>
 static int parts_final_lanes(int nparts) { return nparts >= 1024 ? 256 : (nparts >= 512 ? 128 : 32); }
 
+// the merge of one BatchNorm's records (b null), or of two that take the same form: a row of workgroups each
+static void launch_parts_final_sets(hipStream_t st, const BnPartsFinalSet& a, const BnPartsFinalSet* b, int C, double rows) {
+  // one channel per workgroup above 1024 records — eight records per lane, all in flight at once (level with the two-channel
+  // form on the step, ahead in the family: 407 vs 460 us per step)
+  pick<256, 128, 32>(parts_final_lanes(a.nparts), [&](auto FL) {
+    constexpr int fl = decltype(FL)::value, fc = 256 / fl;
+    const dim3 grid((C + fc - 1) / fc, b ? 2 : 1);
+    if (b) hipLaunchKernelGGL((bn_parts_final_kernel<fc, fl, 2>), grid, dim3(256), 0, st, BnFinalSets<BnPartsFinalSet, 2>{{a, *b}}, C, rows);
+    else hipLaunchKernelGGL((bn_parts_final_kernel<fc, fl, 1>), grid, dim3(256), 0, st, BnFinalSets<BnPartsFinalSet, 1>{{a}}, C, rows);
+    return 0;
+  });
+}
 void launch_parts_final(hipStream_t st, const float* parts, int nparts, int C, double rows, const float* gamma,
                         const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                         float* save_mean, float* save_invstd, float* scale_shift, uint32_t* amax, int pack) {
-  // one channel per workgroup above 1024 records — eight records per lane, all in flight at once (level with the two-channel
-  // form on the step, ahead in the family: 407 vs 460 us per step)
-  const int fl = parts_final_lanes(nparts);
-#define EVK_PARTS_FINAL(FC, FL)                                                                                            \
-  hipLaunchKernelGGL((bn_parts_final_kernel<FC, FL>), dim3((C + FC - 1) / FC), dim3(256), 0, st, parts, nparts, C, rows, gamma, \
-                     beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, scale_shift, amax, pack)
-  if (fl == 256) EVK_PARTS_FINAL(1, 256);
-  else if (fl == 128) EVK_PARTS_FINAL(2, 128);
-  else EVK_PARTS_FINAL(8, 32);
-#undef EVK_PARTS_FINAL
+  const BnPartsFinalSet s = {parts, nparts, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd,
+                             scale_shift, amax, pack};
+  launch_parts_final_sets(st, s, nullptr, C, rows);
 }
 
+// the backward finalisation of one BatchNorm (b null) or two
+static void launch_bn_bwd_final_sets(hipStream_t st, const BnBwdFinalSet& a, const BnBwdFinalSet* b, int nblk, int C,
+                                     int64_t rows) {
+  // (two channels x 128 lanes per workgroup, four times the workgroups, measured -0.2 % chosen from 128 partials up and -2.5 %
+  // everywhere: the 8-byte pieces of a partial row it reads cost more than the shorter chains save — removed)
+  const dim3 grid((C + kFinCh - 1) / kFinCh, b ? 2 : 1);
+  const double inv_rows = 1.0 / (double)rows;
+  if (b) hipLaunchKernelGGL(bn_bwd_final_kernel<2>, grid, dim3(256), 0, st, BnFinalSets<BnBwdFinalSet, 2>{{a, *b}}, nblk, C, inv_rows);
+  else hipLaunchKernelGGL(bn_bwd_final_kernel<1>, grid, dim3(256), 0, st, BnFinalSets<BnBwdFinalSet, 1>{{a}}, nblk, C, inv_rows);
+}
 void launch_bn_bwd_final(hipStream_t st, const float* partial, int nblk, int C, int64_t rows, const float* gamma,
                          const float* invstd, float* dgamma, float* dbeta, float* coef, int train, uint32_t* amax,
                          const float* pmax) {
-  // (two channels x 128 lanes per workgroup, four times the workgroups, measured -0.2 % chosen from 128 partials up and -2.5 %
-  // everywhere: the 8-byte pieces of a partial row it reads cost more than the shorter chains save — removed)
-  hipLaunchKernelGGL(bn_bwd_final_kernel<kFinCh>, dim3((C + kFinCh - 1) / kFinCh), dim3(256), 0, st, partial, nblk, C,
-                     1.0 / (double)rows, gamma, invstd, dgamma, dbeta, coef, train ? 1 : 0, amax, pmax);
+  const BnBwdFinalSet s = {partial, gamma, invstd, dgamma, dbeta, coef, train ? 1 : 0, amax, pmax};
+  launch_bn_bwd_final_sets(st, s, nullptr, nblk, C, rows);
 }
 
-// the forward apply pass over a [rows][C] map (pack: y as packed words, EVK_BN_PACK_Y)
+// the forward apply pass over a [rows][C] map (pack: y as packed words, EVK_BN_PACK_Y); scale_shift_b given: the two-map form,
+// `residual` the shortcut convolution's output (always ReLU and bits, never packed)
 static void launch_bn_apply(hipStream_t st, bool pack, const float* x, const float* residual, const float* scale_shift,
-                            float* y, int64_t rows, int C, uint32_t flags, uint32_t* amax, uint32_t* relu_bits = nullptr) {
+                            float* y, int64_t rows, int C, uint32_t flags, uint32_t* amax, uint32_t* relu_bits = nullptr,
+                            const float* scale_shift_b = nullptr) {
   const size_t n4 = (size_t)rows * C / 4;
-  EVK_BN_LAUNCH_PK(bn_apply_kernel, pack, dim3(oneshot_grid(n4)), 0, st, x, residual, scale_shift, y, n4, C,
-                   (flags & EVK_BN_RELU) ? 1 : 0, amax, relu_bits);
+  const int relu = (flags & EVK_BN_RELU) ? 1 : 0;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(oneshot_grid(n4)), dim3(256), 0, st, x, residual, scale_shift, scale_shift_b, y, n4, C, relu,
+                       amax, relu_bits);
+  };
+  if (scale_shift_b) launch(bn_apply_kernel<false, true>);
+  else if (pack) launch(bn_apply_kernel<true, false>);
+  else launch(bn_apply_kernel<false, false>);
+}
+
+// the backward reduce pass over a [rows][C] map (pmax given: the maxima as well); xb given: over both maps of a block end,
+// the second one's statistics and records in the *_b arguments (mask from `bits`, no d_residual)
+static void launch_bn_bwd_partial(hipStream_t st, const BnPlan& pl, const float* dy, const float* x, const float* y,
+                                  const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                  float* d_residual, float* partial, int64_t rows, int C, int relu, float* pmax,
+                                  const uint32_t* bits, const float* xb = nullptr, const float* mean_b = nullptr,
+                                  const float* invstd_b = nullptr, float* partial_b = nullptr, float* pmax_b = nullptr) {
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(pl.nblk), dim3(256), 0, st, dy, x, xb, y, mean, invstd, mean_b, invstd_b, gamma, beta,
+                       d_residual, partial, partial_b, rows, C, pl.rows_per_blk, pl.tpc, pl.rl, relu, pmax, pmax_b, bits);
+  };
+  if (xb) pmax ? launch(bn_bwd_partial_kernel<2, true>) : launch(bn_bwd_partial_kernel<2, false>);
+  else pmax ? launch(bn_bwd_partial_kernel<1, true>) : launch(bn_bwd_partial_kernel<1, false>);
 }
 
 // ---- The end of a residual block whose shortcut is a convolution (`layerN.0`): out = relu(bn_a(za) + bn_b(zb)), za the
 // main branch's last convolution output, zb the shortcut convolution's.  The passes below take BOTH maps, so the shortcut's
 // normalised copy yb = bn_b(zb) is never stored: forward 3 transfers of the map instead of 5, backward reduce 3 instead of 4,
-// backward apply 5 instead of 6.  New kernels only: the single-map kernels above keep their code.
-
-// y = relu((za*sca + sha) + (zb*scb + shb)), ReLU bits, max|y|: bn_apply_kernel's residual form with the residual computed in
-// registers.  The shortcut term is an expression of its own, so it is rounded as the stored yb was (one fused multiply-add)
-// before the add.
-__global__ __launch_bounds__(256) void bn_apply_dual_kernel(const float* __restrict__ za, const float* __restrict__ zb,
-                                                            const float* __restrict__ scale_shift_a,
-                                                            const float* __restrict__ scale_shift_b, float* __restrict__ y,
-                                                            size_t n4, int C, uint32_t* __restrict__ amax,
-                                                            uint32_t* __restrict__ relu_bits) {
-  const size_t base = (size_t)bn_blk() * 256;
-  const size_t i = base + threadIdx.x;
-  const bool valid = i < n4;
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (valid) {
-    const int c4 = C >> 2;
-    const int cb = chunk_of(base, c4);
-    const f32x4 sca = reinterpret_cast<const f32x4*>(scale_shift_a)[cb];
-    const f32x4 sha = reinterpret_cast<const f32x4*>(scale_shift_a + C)[cb];
-    const f32x4 scb = reinterpret_cast<const f32x4*>(scale_shift_b)[cb];
-    const f32x4 shb = reinterpret_cast<const f32x4*>(scale_shift_b + C)[cb];
-    const f32x4 yb = bn_ld(zb, i) * scb + shb;
-    v = bn_ld(za, i) * sca + sha;
-    v += yb;
-  }
-  // every lane of a wave takes part (v = 0 where the element does not exist); a wave wholly past the end has no chunk
-  if (((i >> 6) << 6) < n4) relu_bits_store(relu_bits, i >> 6, v.x > 0.f, v.y > 0.f, v.z > 0.f, v.w > 0.f);
-  if (valid) {
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    reinterpret_cast<f32x4*>(y)[i] = v;
-  }
-  if (amax) block_absmax(v, valid, amax);   // all lanes of the workgroup arrive here together
-}
-
-// Backward stage 1 for both maps: g = dy where the block's ReLU bit is set, masked ONCE;
-// partial_a[blk] = (sum g, sum g * xhat_a), partial_b[blk] = (sum g, sum g * xhat_b) — bn_bwd_partial_kernel's plan, row
-// order and fold, so each record has the bits the single-map pass gives.  PK: pmax_a / pmax_b as bn_bwd_partial_kernel<true>.
-template <bool PK>
-__global__ __launch_bounds__(256) void bn_bwd_partial_dual_kernel(
-    const float* __restrict__ dy, const float* __restrict__ xa, const float* __restrict__ xb,
-    const float* __restrict__ mean_a, const float* __restrict__ invstd_a, const float* __restrict__ mean_b,
-    const float* __restrict__ invstd_b, float* __restrict__ partial_a, float* __restrict__ partial_b, int64_t rows, int C,
-    int64_t rows_per_blk, int tpc, int rl, float* __restrict__ pmax_a, float* __restrict__ pmax_b,
-    const uint32_t* __restrict__ bits) {
-  __shared__ f32x4 red[2][256];
-  const int c4 = C >> 2;
-  const int tc = threadIdx.x % tpc, tr = threadIdx.x / tpc;
-  const int64_t r0 = (int64_t)bn_blk() * rows_per_blk;
-  const int64_t r1 = min(rows, r0 + rows_per_blk);
-  for (int cb = tc; cb < c4; cb += tpc) {
-    const f32x4 mua = *reinterpret_cast<const f32x4*>(mean_a + cb * 4);
-    const f32x4 isa = *reinterpret_cast<const f32x4*>(invstd_a + cb * 4);
-    const f32x4 mub = *reinterpret_cast<const f32x4*>(mean_b + cb * 4);
-    const f32x4 isb = *reinterpret_cast<const f32x4*>(invstd_b + cb * 4);
-    f32x4 s = {0.f, 0.f, 0.f, 0.f}, qa = {0.f, 0.f, 0.f, 0.f}, qb = {0.f, 0.f, 0.f, 0.f};
-    f32x4 gm = {0.f, 0.f, 0.f, 0.f}, xma = {0.f, 0.f, 0.f, 0.f}, xmb = {0.f, 0.f, 0.f, 0.f};
-    if (tr < rl) {
-      auto one = [&](const f32x4 gin, const f32x4 xva, const f32x4 xvb, size_t off) {
-        const f32x4 g = relu_bits_mask(gin, bits, off >> 2);
-        s += g;
-        const f32x4 xha = (xva - mua) * isa;
-        qa += g * xha;
-        const f32x4 xhb = (xvb - mub) * isb;
-        qb += g * xhb;
-        if constexpr (PK) {
-          gm.x = fmaxf(gm.x, fabsf(g.x)); gm.y = fmaxf(gm.y, fabsf(g.y));
-          gm.z = fmaxf(gm.z, fabsf(g.z)); gm.w = fmaxf(gm.w, fabsf(g.w));
-          xma.x = fmaxf(xma.x, fabsf(xha.x)); xma.y = fmaxf(xma.y, fabsf(xha.y));
-          xma.z = fmaxf(xma.z, fabsf(xha.z)); xma.w = fmaxf(xma.w, fabsf(xha.w));
-          xmb.x = fmaxf(xmb.x, fabsf(xhb.x)); xmb.y = fmaxf(xmb.y, fabsf(xhb.y));
-          xmb.z = fmaxf(xmb.z, fabsf(xhb.z)); xmb.w = fmaxf(xmb.w, fabsf(xhb.w));
-        }
-      };
-      int64_t r = r0 + tr;
-      const int64_t st = rl;
-      // four rows per trip: 12 independent 16-byte loads in flight per lane
-      for (; r + 3 * st < r1; r += 4 * st) {
-        const size_t o0 = (size_t)r * C + cb * 4, o1 = (size_t)(r + st) * C + cb * 4;
-        const size_t o2 = (size_t)(r + 2 * st) * C + cb * 4, o3 = (size_t)(r + 3 * st) * C + cb * 4;
-        const f32x4 g0 = bp_ld(dy + o0), g1 = bp_ld(dy + o1);
-        const f32x4 g2 = bp_ld(dy + o2), g3 = bp_ld(dy + o3);
-        const f32x4 a0 = bp_ld(xa + o0), a1 = bp_ld(xa + o1);
-        const f32x4 a2 = bp_ld(xa + o2), a3 = bp_ld(xa + o3);
-        const f32x4 b0 = bp_ld(xb + o0), b1 = bp_ld(xb + o1);
-        const f32x4 b2 = bp_ld(xb + o2), b3 = bp_ld(xb + o3);
-        one(g0, a0, b0, o0);
-        one(g1, a1, b1, o1);
-        one(g2, a2, b2, o2);
-        one(g3, a3, b3, o3);
-      }
-      for (; r < r1; r += st) {
-        const size_t o0 = (size_t)r * C + cb * 4;
-        one(bp_ld(dy + o0), bp_ld(xa + o0), bp_ld(xb + o0), o0);
-      }
-    }
-    fold_store_record(red, s, qa, partial_a, bn_blk(), C, cb, tc, tr, tpc, rl);
-    fold_store_record(red, s, qb, partial_b, bn_blk(), C, cb, tc, tr, tpc, rl);
-    if constexpr (PK) {
-      red[0][threadIdx.x] = gm;
-      red[1][threadIdx.x] = xma;
-      __syncthreads();
-      if (tr == 0) {
-        for (int k = 1; k < rl; ++k) {
-          const f32x4 a = red[0][k * tpc + tc], b = red[1][k * tpc + tc];
-          gm.x = fmaxf(gm.x, a.x); gm.y = fmaxf(gm.y, a.y); gm.z = fmaxf(gm.z, a.z); gm.w = fmaxf(gm.w, a.w);
-          xma.x = fmaxf(xma.x, b.x); xma.y = fmaxf(xma.y, b.y); xma.z = fmaxf(xma.z, b.z); xma.w = fmaxf(xma.w, b.w);
-        }
-      }
-      __syncthreads();
-      red[0][threadIdx.x] = xmb;
-      __syncthreads();
-      if (tr == 0) {
-        for (int k = 1; k < rl; ++k) {
-          const f32x4 b = red[0][k * tpc + tc];
-          xmb.x = fmaxf(xmb.x, b.x); xmb.y = fmaxf(xmb.y, b.y); xmb.z = fmaxf(xmb.z, b.z); xmb.w = fmaxf(xmb.w, b.w);
-        }
-        float* oa = pmax_a + (size_t)bn_blk() * 2 * C;
-        float* ob = pmax_b + (size_t)bn_blk() * 2 * C;
-        *reinterpret_cast<f32x4*>(oa + cb * 4) = gm;
-        *reinterpret_cast<f32x4*>(oa + C + cb * 4) = xma;
-        *reinterpret_cast<f32x4*>(ob + cb * 4) = gm;
-        *reinterpret_cast<f32x4*>(ob + C + cb * 4) = xmb;
-      }
-      __syncthreads();
-    }
-  }
-}
+// backward apply 5 instead of 6.  Each pass is a form of the single-map pass above, not a copy of it: the forward apply is
+// bn_apply_kernel<false, true> (the added term computed from zb in registers), the backward reduce bn_bwd_partial_kernel<2, PK>,
+// both finalisations their kernels with a second row of workgroups; the backward apply below is a kernel of its own (two
+// outputs, each packed or not) built from bn_bwd_apply_kernel's per-map step, bn_dx_store.
 
 // Backward stage 3 for both maps: dxa = ka0 * (g - ka1 - xhat_a*ka2), dxb likewise from the second coefficient set; g is
 // read and masked once.  PKA / PKB: that output packed under the bound its finalisation left in slot 0 of its `amax`.
@@ -708,34 +649,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_dual_kernel(
     const int c4 = C >> 2;
     const int c = chunk_of(base, c4);
     const f32x4 g = relu_bits_mask(bn_ld(dy, i), bits, i);
-    {
-      const f32x4 k0 = reinterpret_cast<const f32x4*>(coef_a)[c];
-      const f32x4 k1 = reinterpret_cast<const f32x4*>(coef_a + C)[c];
-      const f32x4 k2 = reinterpret_cast<const f32x4*>(coef_a + 2 * C)[c];
-      const f32x4 mu = reinterpret_cast<const f32x4*>(mean_a)[c];
-      const f32x4 is = reinterpret_cast<const f32x4*>(invstd_a)[c];
-      const f32x4 xh = (bn_ld(xa, i) - mu) * is;
-      outa = k0 * (g - k1 - xh * k2);
-      if constexpr (PKA) {
-        reinterpret_cast<u32x4*>(dxa)[i] = pack_hl4(outa, pk_inv_a);
-      } else {
-        reinterpret_cast<f32x4*>(dxa)[i] = outa;
-      }
-    }
-    {
-      const f32x4 k0 = reinterpret_cast<const f32x4*>(coef_b)[c];
-      const f32x4 k1 = reinterpret_cast<const f32x4*>(coef_b + C)[c];
-      const f32x4 k2 = reinterpret_cast<const f32x4*>(coef_b + 2 * C)[c];
-      const f32x4 mu = reinterpret_cast<const f32x4*>(mean_b)[c];
-      const f32x4 is = reinterpret_cast<const f32x4*>(invstd_b)[c];
-      const f32x4 xh = (bn_ld(xb, i) - mu) * is;
-      outb = k0 * (g - k1 - xh * k2);
-      if constexpr (PKB) {
-        reinterpret_cast<u32x4*>(dxb)[i] = pack_hl4(outb, pk_inv_b);
-      } else {
-        reinterpret_cast<f32x4*>(dxb)[i] = outb;
-      }
-    }
+    const BnDxCoef ka = bn_dx_coef(coef_a, mean_a, invstd_a, C, c);
+    outa = bn_dx_store<PKA>(ka, g, bn_ld(xa, i), dxa, i, pk_inv_a);
+    const BnDxCoef kb = bn_dx_coef(coef_b, mean_b, invstd_b, C, c);
+    outb = bn_dx_store<PKB>(kb, g, bn_ld(xb, i), dxb, i, pk_inv_b);
   }
   // all lanes of the workgroup arrive here together; block_absmax's LDS words are free again after the barrier between
   if constexpr (!PKA)
@@ -883,8 +800,8 @@ extern "C" int evk_bn_bwd_bits(const float* dy, const float* x, const float* y, 
   const bool pack = (flags & EVK_BN_PACK_DX) != 0;
   EVK_REQUIRE(!pack || dx_absmax, EVK_E_INVALID, "bn_bwd: EVK_BN_PACK_DX needs dx_absmax (slots zero on entry)");
   float* pmax = pack ? ws.pmax : nullptr;
-  EVK_BN_LAUNCH_PK(bn_bwd_partial_kernel, pack, dim3(pl.nblk), 0, st, dy, x, y, save_mean, save_invstd, gamma, beta, d_residual,
-                   ws.partial, rows, C, pl.rows_per_blk, pl.tpc, pl.rl, relu, pmax, relu_bits);
+  launch_bn_bwd_partial(st, pl, dy, x, y, save_mean, save_invstd, gamma, beta, d_residual, ws.partial, rows, C, relu, pmax,
+                        relu_bits);
   rc = check_launch("bn_bwd_partial");
   if (rc) return rc;
   launch_bn_bwd_final(st, ws.partial, pl.nblk, C, rows, gamma, save_invstd, dgamma, dbeta, ws.coef, train, dx_absmax, pmax);
@@ -907,7 +824,7 @@ extern "C" int evk_bn_bwd(const float* dy, const float* x, const float* y, const
                          workspace, workspace_bytes, dx_absmax, nullptr, stream);
 }
 
-// ---- Both BatchNorms at the end of a residual block with a shortcut convolution (bn_apply_dual_kernel and its neighbours).
+// ---- Both BatchNorms at the end of a residual block with a shortcut convolution (the two-map forms of the passes above).
 // Training mode, both statistics from epilogue records.  workspace: TWO single-map workspaces back to back
 // (2 * evk_bn_workspace_bytes): the main branch's records and coefficients in the first, the shortcut's in the second.
 extern "C" int evk_bn_fwd_train_parts_dual(const float* za, const float* zb, const float* gamma_a, const float* beta_a,
@@ -927,33 +844,23 @@ extern "C" int evk_bn_fwd_train_parts_dual(const float* za, const float* zb, con
   float* ss_a = BnWorkspace(workspace, C).coef;
   float* ss_b = BnWorkspace((char*)workspace + BnWorkspace::bytes(C), C).coef;
   // only the main branch's finalisation owns the slots of y_absmax
-  const int fl = parts_final_lanes(nparts_a);
-  if (fl == parts_final_lanes(nparts_b)) {   // the same form of the merge for both: one launch, a row of workgroups each
-    const BnPartsFinalSet sa = {parts_a, nparts_a, gamma_a, beta_a, running_mean_a, running_var_a, momentum_a, eps_a,
-                                save_mean_a, save_invstd_a, ss_a, y_absmax};
-    const BnPartsFinalSet sb = {parts_b, nparts_b, gamma_b, beta_b, running_mean_b, running_var_b, momentum_b, eps_b,
-                                save_mean_b, save_invstd_b, ss_b, nullptr};
-#define EVK_PARTS_FINAL_DUAL(FC, FL)                                                                                       \
-  hipLaunchKernelGGL((bn_parts_final_dual_kernel<FC, FL>), dim3((C + FC - 1) / FC, 2), dim3(256), 0, st, sa, sb, C, (double)rows)
-    if (fl == 256) EVK_PARTS_FINAL_DUAL(1, 256);
-    else if (fl == 128) EVK_PARTS_FINAL_DUAL(2, 128);
-    else EVK_PARTS_FINAL_DUAL(8, 32);
-#undef EVK_PARTS_FINAL_DUAL
+  const BnPartsFinalSet sa = {parts_a, nparts_a, gamma_a, beta_a, running_mean_a, running_var_a, momentum_a, eps_a,
+                              save_mean_a, save_invstd_a, ss_a, y_absmax, 0};
+  const BnPartsFinalSet sb = {parts_b, nparts_b, gamma_b, beta_b, running_mean_b, running_var_b, momentum_b, eps_b,
+                              save_mean_b, save_invstd_b, ss_b, nullptr, 0};
+  if (parts_final_lanes(nparts_a) == parts_final_lanes(nparts_b)) {   // the same form of the merge for both: one launch
+    launch_parts_final_sets(st, sa, &sb, C, (double)rows);
     rc = check_launch("bn_parts_final_dual");
     if (rc) return rc;
   } else {
-    launch_parts_final(st, parts_b, nparts_b, C, (double)rows, gamma_b, beta_b, running_mean_b, running_var_b, momentum_b,
-                       eps_b, save_mean_b, save_invstd_b, ss_b, nullptr, 0);
+    launch_parts_final_sets(st, sb, nullptr, C, (double)rows);
     rc = check_launch("bn_parts_final");
     if (rc) return rc;
-    launch_parts_final(st, parts_a, nparts_a, C, (double)rows, gamma_a, beta_a, running_mean_a, running_var_a, momentum_a,
-                       eps_a, save_mean_a, save_invstd_a, ss_a, y_absmax, 0);
+    launch_parts_final_sets(st, sa, nullptr, C, (double)rows);
     rc = check_launch("bn_parts_final");
     if (rc) return rc;
   }
-  const size_t n4 = (size_t)rows * C / 4;
-  hipLaunchKernelGGL(bn_apply_dual_kernel, dim3(oneshot_grid(n4)), dim3(256), 0, st, za, zb, (const float*)ss_a,
-                     (const float*)ss_b, y, n4, C, y_absmax, relu_bits);
+  launch_bn_apply(st, false, za, zb, ss_a, y, rows, C, EVK_BN_RELU, y_absmax, relu_bits, ss_b);
   return check_launch("bn_apply_dual");
 }
 
@@ -989,15 +896,13 @@ extern "C" int evk_bn_bwd_dual(const float* dy, const float* za, const float* zb
   const BnPlan pl = bn_plan(rows, C);
   const BnWorkspace wa(workspace, C), wb((char*)workspace + BnWorkspace::bytes(C), C);
   const bool pack = pack_a || pack_b;
-  EVK_BN_LAUNCH_PK(bn_bwd_partial_dual_kernel, pack, dim3(pl.nblk), 0, st, dy, za, zb, save_mean_a, save_invstd_a, save_mean_b,
-                   save_invstd_b, wa.partial, wb.partial, rows, C, pl.rows_per_blk, pl.tpc, pl.rl, pack ? wa.pmax : nullptr,
-                   pack ? wb.pmax : nullptr, relu_bits);
+  launch_bn_bwd_partial(st, pl, dy, za, nullptr, save_mean_a, save_invstd_a, nullptr, nullptr, nullptr, wa.partial, rows, C, 3,
+                        pack ? wa.pmax : nullptr, relu_bits, zb, save_mean_b, save_invstd_b, wb.partial, pack ? wb.pmax : nullptr);
   rc = check_launch("bn_bwd_partial_dual");
   if (rc) return rc;
-  const BnBwdFinalSet fa = {wa.partial, gamma_a, save_invstd_a, dgamma_a, dbeta_a, wa.coef, dza_absmax, pack_a ? wa.pmax : nullptr};
-  const BnBwdFinalSet fb = {wb.partial, gamma_b, save_invstd_b, dgamma_b, dbeta_b, wb.coef, dzb_absmax, pack_b ? wb.pmax : nullptr};
-  hipLaunchKernelGGL(bn_bwd_final_dual_kernel, dim3((C + kFinCh - 1) / kFinCh, 2), dim3(256), 0, st, fa, fb, pl.nblk, C,
-                     1.0 / (double)rows);
+  const BnBwdFinalSet fa = {wa.partial, gamma_a, save_invstd_a, dgamma_a, dbeta_a, wa.coef, 1, dza_absmax, pack_a ? wa.pmax : nullptr};
+  const BnBwdFinalSet fb = {wb.partial, gamma_b, save_invstd_b, dgamma_b, dbeta_b, wb.coef, 1, dzb_absmax, pack_b ? wb.pmax : nullptr};
+  launch_bn_bwd_final_sets(st, fa, &fb, pl.nblk, C, rows);
   rc = check_launch("bn_bwd_final_dual");
   if (rc) return rc;
   const size_t n4 = (size_t)rows * C / 4;
@@ -1160,8 +1065,7 @@ extern "C" int evk_bn_bwd_local_sums(const float* dy, const float* x, const floa
   hipStream_t st = (hipStream_t)stream;
   const BnPlan pl = bn_plan(rows, C);
   float* partial = (float*)workspace;
-  hipLaunchKernelGGL(bn_bwd_partial_kernel<false>, dim3(pl.nblk), dim3(256), 0, st, dy, x, y, mean, invstd, gamma, beta,
-                     d_residual, partial, rows, C, pl.rows_per_blk, pl.tpc, pl.rl, relu, (float*)nullptr);
+  launch_bn_bwd_partial(st, pl, dy, x, y, mean, invstd, gamma, beta, d_residual, partial, rows, C, relu, nullptr, nullptr);
   rc = check_launch("bn_bwd_partial");
   if (rc) return rc;
   hipLaunchKernelGGL(bn_bwd_sums_final_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(256), 0, st, (const float*)partial,

@@ -112,11 +112,12 @@ __device__ __forceinline__ f32x4 relu_mask(f32x4 g, const f32x4 yy) {
 // End of a reduce pass's trip over channel chunk cb: fold the sums (s, q) over the chunk's rl row lanes through the kernel's
 // red[2][256] (thread = tr * tpc + tc) and store workgroup blk's record rec[blk][0][C] = s, [1][C] = q.  Every thread of the
 // workgroup arrives; red is free again on return.
-// (Three neighbours keep their own text, because the split that introduced this header left every kernel's instructions as
-// they were and these came out reordered, registers unchanged: the fold of MAXIMA in bn_bwd_partial_kernel<true> written as a
-// variant of this helper — template flag, functor, reference or record-pointer parameters alike; gn_partial_kernel
-// (groupnorm.hip) through this helper; the (mu, is, sc, sh) channel prologue of the reduce and pool passes as one helper,
-// whose loads also moved across the gather in bn_pool_bwd_apply_kernel: 57 -> 63 VGPRs.)
+// (Two neighbours keep their own text, because the split that introduced this header left every kernel's instructions as
+// they were and these came out reordered, registers unchanged: gn_partial_kernel (groupnorm.hip) through this helper; the
+// (mu, is, sc, sh) channel prologue of the reduce and pool passes as one helper, whose loads also moved across the gather in
+// bn_pool_bwd_apply_kernel: 57 -> 63 VGPRs.  The fold of MAXIMA, fold_store_maxima below, is a function of its own for the
+// same reason: written as a variant of this one — template flag, functor, reference or record-pointer parameters alike —
+// it came out reordered.)
 __device__ __forceinline__ void fold_store_record(f32x4 (*red)[256], f32x4 s, f32x4 q, float* rec, size_t blk, int C, int cb,
                                                   int tc, int tr, int tpc, int rl) {
   red[0][threadIdx.x] = s;
@@ -130,6 +131,32 @@ __device__ __forceinline__ void fold_store_record(f32x4 (*red)[256], f32x4 s, f3
     float* o = rec + blk * 2 * C;
     *reinterpret_cast<f32x4*>(o + cb * 4) = s;
     *reinterpret_cast<f32x4*>(o + C + cb * 4) = q;
+  }
+  __syncthreads();
+}
+
+// m = max(m, v) / max(m, |v|) per component
+__device__ __forceinline__ void max4(f32x4& m, const f32x4 v) {
+  m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+}
+__device__ __forceinline__ void absmax4(f32x4& m, const f32x4 v) {
+  m.x = fmaxf(m.x, fabsf(v.x)); m.y = fmaxf(m.y, fabsf(v.y)); m.z = fmaxf(m.z, fabsf(v.z)); m.w = fmaxf(m.w, fabsf(v.w));
+}
+
+// fold_store_record for a record of maxima (packed dx): rec[blk][0][C] = max |g|, [1][C] = max |xhat| over the chunk's rows
+__device__ __forceinline__ void fold_store_maxima(f32x4 (*red)[256], f32x4 gm, f32x4 xm, float* rec, size_t blk, int C, int cb,
+                                                  int tc, int tr, int tpc, int rl) {
+  red[0][threadIdx.x] = gm;
+  red[1][threadIdx.x] = xm;
+  __syncthreads();
+  if (tr == 0) {
+    for (int k = 1; k < rl; ++k) {
+      max4(gm, red[0][k * tpc + tc]);
+      max4(xm, red[1][k * tpc + tc]);
+    }
+    float* o = rec + blk * 2 * C;
+    *reinterpret_cast<f32x4*>(o + cb * 4) = gm;
+    *reinterpret_cast<f32x4*>(o + C + cb * 4) = xm;
   }
   __syncthreads();
 }
@@ -215,7 +242,7 @@ void launch_parts_final(hipStream_t st, const float* parts, int nparts, int C, d
                         const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                         float* save_mean, float* save_invstd, float* scale_shift, uint32_t* amax, int pack);
 // Backward finalisation of nblk partial records (and their maxima pmax, or null) into dgamma, dbeta, coef:
-// bn_bwd_final_kernel<kFinCh>
+// bn_bwd_final_kernel
 void launch_bn_bwd_final(hipStream_t st, const float* partial, int nblk, int C, int64_t rows, const float* gamma,
                          const float* invstd, float* dgamma, float* dbeta, float* coef, int train, uint32_t* amax,
                          const float* pmax);

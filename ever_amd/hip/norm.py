@@ -19,6 +19,38 @@ from ._base import (  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------ batch norm
+def _dx_scale(dev, want):
+    """(scale buffer, packed) of a gradient that is its producing convolution's dy and — where that convolution said so in
+    forward (`want`) — nothing else: written packed under a scale bounded before the apply pass (EVK_BN_PACK_DX)"""
+    pack = want and _f16x2()
+    abits = _amax_zeroed(dev) if pack else _amax_out(dev)
+    return abits, bool(pack and abits is not None)
+
+
+def _hand_scale(t, abits, packed):
+    """t goes on as packed words under the scale in abits, or as fp32 with its max|t| there"""
+    if packed:
+        _mark_packed(t, abits)
+    elif abits is not None:
+        _note_amax(t, abits)
+    return t
+
+
+def _take_handoff(y):
+    """a forward pass left (scale buffer, packed) of y in _AMAX_HANDOFF: y is the next convolution's operand"""
+    if _AMAX_HANDOFF[0] is not None:
+        _hand_scale(y, *_AMAX_HANDOFF[0])
+        _AMAX_HANDOFF[0] = None
+    return y
+
+
+def _affine_grads(weight, c, dev):
+    """(dgamma, dbeta) to write into, or (None, None) for a BatchNorm without affine parameters"""
+    if weight is None:
+        return None, None
+    return torch.empty((c,), device=dev, dtype=torch.float32), torch.empty((c,), device=dev, dtype=torch.float32)
+
+
 class _BatchNormActFn(Function):
     """BatchNorm2d (+ residual add) (+ ReLU) in one pass.
 
@@ -104,16 +136,10 @@ class _BatchNormActFn(Function):
         need_res = ctx.has_res and ctx.needs_input_grad[1]
         lazy = need_res and ctx.lazy_res and rbits is not None and in_bits is None
         dres = torch.empty_like(x) if (need_res and not lazy) else None
-        has_affine = weight is not None
-        dgamma = torch.empty((c,), device=dev, dtype=torch.float32) if has_affine else None
-        dbeta = torch.empty((c,), device=dev, dtype=torch.float32) if has_affine else None
+        dgamma, dbeta = _affine_grads(weight, c, dev)
         # reduce pass reads dy, x (+y mask); apply pass reads g, x and writes dx (+ the residual gradient write)
         nb = 4.0 * x.numel() * (5 + (1 if y is not None else 0) + (1 if dres is not None else 0))
-        # dx is the producing convolution's dy (data and weight gradient operand) — and, when that convolution said so
-        # in forward, nothing else: written packed under a scale bounded before the apply pass (EVK_BN_PACK_DX)
-        pack = ctx.pack_dx and _f16x2()
-        abits = _amax_zeroed(dev) if pack else _amax_out(dev)
-        pack = pack and abits is not None
+        abits, pack = _dx_scale(dev, ctx.pack_dx)
         mask_bits = rbits if rbits is not None else in_bits
         if in_bits is not None:
             relu_bits_stats['masked_bn'] += 1
@@ -127,10 +153,7 @@ class _BatchNormActFn(Function):
             dres = dy.view_as(dy)
             dres._evk_relu_bits = (dres._version, dres.data_ptr(), rbits)
             _inherit_amax(dres, dy)
-        if pack:
-            _mark_packed(dx, abits)
-        elif abits is not None:
-            _note_amax(dx, abits)
+        _hand_scale(dx, abits, pack)
         if ctx.has_res and not need_res:
             dres = None
         return (dx, dres, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None,
@@ -159,14 +182,7 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, training, momentu
         weight_planes.note_running_stats_changed()
     y = _BatchNormActFn.apply(x, residual, weight, bias, running_mean, running_var, bool(use_batch_stats),
                               0.0 if momentum is None else momentum, eps, bool(relu), parts, bool(pack_out), bool(lazy_res))
-    if _AMAX_HANDOFF[0] is not None:       # the pass left max|y| (or its bound) there: y is the next convolution's operand
-        abits, packed = _AMAX_HANDOFF[0]
-        if packed:
-            _mark_packed(y, abits)
-        elif abits is not None:
-            _note_amax(y, abits)
-        _AMAX_HANDOFF[0] = None
-    return y
+    return _take_handoff(y)
 
 
 # The end of a residual block whose shortcut is a convolution: both BatchNorms in passes that take both maps (EVK_BN_DUAL=0:
@@ -182,7 +198,7 @@ def bn_dual_enabled():
 class _BatchNormDualFn(Function):
     """relu(bn_a(za) + bn_b(zb)) — the last BatchNorm of a residual block and the BatchNorm of its shortcut convolution
     (reference ever/module/_resnets.py:108-112 with `downsample`) — without storing bn_b(zb) or reading dy and the ReLU
-    bits twice in the backward (csrc/bn.hip: bn_apply_dual_kernel, bn_bwd_partial_dual_kernel, bn_bwd_apply_dual_kernel).
+    bits twice in the backward (csrc/bn.hip: bn_apply_kernel<false, true>, bn_bwd_partial_kernel<2, PK>, bn_bwd_apply_dual_kernel).
     Training mode, both statistics from the convolutions' epilogue records.  The same bits as _BatchNormActFn twice."""
 
     @staticmethod
@@ -226,33 +242,19 @@ class _BatchNormDualFn(Function):
         ws_bytes = 2 * lib.evk_bn_workspace_bytes(rows, c)
         ws = workspace(dev, ws_bytes)
         dza, dzb = torch.empty_like(za), torch.empty_like(zb)
-
-        def affine_grads(weight):
-            if weight is None:
-                return None, None
-            return (torch.empty((c,), device=dev, dtype=torch.float32), torch.empty((c,), device=dev, dtype=torch.float32))
-        dgamma_a, dbeta_a = affine_grads(weight_a)
-        dgamma_b, dbeta_b = affine_grads(weight_b)
-        # each output is its producing convolution's dy and nothing else where that convolution said so (EVK_BN_PACK_DX)
-        packs, scales = [], []
-        for want in ctx.pack_dx:
-            pack = want and _f16x2()
-            abits = _amax_zeroed(dev) if pack else _amax_out(dev)
-            packs.append(bool(pack and abits is not None))
-            scales.append(abits)
+        dgamma_a, dbeta_a = _affine_grads(weight_a, c, dev)
+        dgamma_b, dbeta_b = _affine_grads(weight_b, c, dev)
+        (scale_a, pack_a), (scale_b, pack_b) = (_dx_scale(dev, want) for want in ctx.pack_dx)
         # reduce pass reads dy and both maps; apply pass reads them again and writes both gradients
         relu_bits_stats['lazy'] += 1          # the shortcut's share of dy is never written masked ...
         relu_bits_stats['masked_bn'] += 1     # ... its BatchNorm masks it in the pass it shares with the block's last one
         _timed_call('bn', 4.0 * za.numel() * 8, 'evk_bn_bwd_dual', dy.data_ptr(), za.data_ptr(), zb.data_ptr(), _ptr(weight_a),
                     mean_a.data_ptr(), invstd_a.data_ptr(), _ptr(weight_b), mean_b.data_ptr(), invstd_b.data_ptr(),
                     dza.data_ptr(), dzb.data_ptr(), _ptr(dgamma_a), _ptr(dbeta_a), _ptr(dgamma_b), _ptr(dbeta_b), rows, c,
-                    2 if packs[0] else 0, 2 if packs[1] else 0, ws.data_ptr(), ws_bytes, _ptr(scales[0]), _ptr(scales[1]),
+                    2 if pack_a else 0, 2 if pack_b else 0, ws.data_ptr(), ws_bytes, _ptr(scale_a), _ptr(scale_b),
                     rbits.data_ptr(), st)
-        for dz, pack, abits in ((dza, packs[0], scales[0]), (dzb, packs[1], scales[1])):
-            if pack:
-                _mark_packed(dz, abits)
-            elif abits is not None:
-                _note_amax(dz, abits)
+        _hand_scale(dza, scale_a, pack_a)
+        _hand_scale(dzb, scale_b, pack_b)
         need = ctx.needs_input_grad
         return (dza, dzb, dgamma_a if need[2] else None, dbeta_a if need[3] else None, None, None, None, None,
                 dgamma_b if need[8] else None, dbeta_b if need[9] else None, None, None, None, None, None, None)
@@ -282,12 +284,7 @@ def batch_norm_act_dual(za, bn_a, zb, bn_b):
         args.append((bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
                      bn.momentum, bn.eps))
     _AMAX_HANDOFF[0] = None
-    y = _BatchNormDualFn.apply(za, zb, *args[1], *args[0], pa, pb)
-    if _AMAX_HANDOFF[0] is not None:
-        if _AMAX_HANDOFF[0][0] is not None:
-            _note_amax(y, _AMAX_HANDOFF[0][0])
-        _AMAX_HANDOFF[0] = None
-    return y
+    return _take_handoff(_BatchNormDualFn.apply(za, zb, *args[1], *args[0], pa, pb))
 
 
 class _BnReluPoolFn(Function):
@@ -327,17 +324,14 @@ class _BnReluPoolFn(Function):
         ws_bytes = _C.load().evk_bn_workspace_bytes(n * h * w, c)
         ws = workspace(dev, ws_bytes)
         dx = torch.empty_like(x)
-        has_affine = weight is not None
-        dgamma = torch.empty((c,), device=dev, dtype=torch.float32) if has_affine else None
-        dbeta = torch.empty((c,), device=dev, dtype=torch.float32) if has_affine else None
+        dgamma, dbeta = _affine_grads(weight, c, dev)
         abits = _amax_out(dev)
         # both passes read x, the pooled gradient and the codes; the apply pass writes dx
         nb = 4.0 * x.numel() * 3 + 2 * 5.0 * dp.numel()
         _timed_call('bn', nb, 'evk_bn_relu_pool_bwd', dp.data_ptr(), code.data_ptr(), x.data_ptr(), _ptr(weight), _ptr(bias),
                     save_mean.data_ptr(), save_invstd.data_ptr(), dx.data_ptr(), _ptr(dgamma), _ptr(dbeta), n, h, w, c, 1,
                     ws.data_ptr(), ws_bytes, _ptr(abits), st)
-        if abits is not None:
-            _note_amax(dx, abits)
+        _hand_scale(dx, abits, False)
         return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None)
 
@@ -360,12 +354,8 @@ def batch_norm_relu_max_pool(x, weight, bias, running_mean, running_var, momentu
     _AMAX_HANDOFF[0] = None
     if running_mean is not None:
         weight_planes.note_running_stats_changed()
-    y = _BnReluPoolFn.apply(x, weight, bias, running_mean, running_var, 0.0 if momentum is None else momentum, eps, parts)
-    if _AMAX_HANDOFF[0] is not None:
-        if _AMAX_HANDOFF[0][0] is not None:
-            _note_amax(y, _AMAX_HANDOFF[0][0])
-        _AMAX_HANDOFF[0] = None
-    return y
+    return _take_handoff(_BnReluPoolFn.apply(x, weight, bias, running_mean, running_var, 0.0 if momentum is None else momentum,
+                                             eps, parts))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,10 +1,10 @@
-"""The two-map BatchNorm passes at the end of a residual block with a shortcut convolution (csrc/bn.hip: bn_apply_dual_kernel,
-bn_bwd_partial_dual_kernel, bn_bwd_apply_dual_kernel; include/ever_hip.h: evk_bn_fwd_train_parts_dual, evk_bn_bwd_dual),
+"""The two-map BatchNorm passes at the end of a residual block with a shortcut convolution (csrc/bn.hip: the two-map forms of
+bn_apply_kernel and bn_bwd_partial_kernel, bn_bwd_apply_dual_kernel; include/ever_hip.h: evk_bn_fwd_train_parts_dual, evk_bn_bwd_dual),
 through the C-ABI, BIT FOR BIT against the two-call path they replace: evk_bn_fwd_train_parts on the shortcut map, then
 evk_bn_fwd_train_parts_bits on the main map with that result as the residual; evk_bn_bwd_bits on each map in the backward.
 
 Shapes are the smallest at which each code path can go wrong, and every case asserts with the host-only evk_bn_plan that it
-still has the property it is there for.  Outputs and workspaces of the two-map path hold NaN before a launch and sit inside
+still has the property it is there for.  Outputs and workspaces of BOTH paths hold NaN before a launch and sit inside
 sentinel-guarded allocations (tests/guard_common.py).  One case is also held against float64 under the bounds
 tests/test_bn_gpu.py derives."""
 import itertools
@@ -79,7 +79,7 @@ def _forward_pair(lib, dev, za, zb, pa, pb, reca, recb, rm0, rv0, dual, bufs):
     rows, c = za.shape
     st = _stream()
     (ga, ba), (gb, bb) = pa, pb
-    new = bufs.out if dual else (lambda n, dtype=torch.float32: torch.full((n,), float('nan'), device=dev).view(dtype)[:n])
+    new = bufs.out
     y, sma, sia, smb, sib = new(rows * c), new(c), new(c), new(c), new(c)
     bits = new(lib.evk_relu_bits_bytes(rows * c) // 4, torch.int32)
     rma, rva, rmb, rvb = (t.clone() for t in (rm0[0], rv0[0], rm0[1], rv0[1]))
@@ -108,7 +108,7 @@ def _backward_pair(lib, dev, dy, za, zb, pa, pb, fwd, pack_a, pack_b, dual, bufs
     rows, c = za.shape
     st = _stream()
     (ga, ba), (gb, bb) = pa, pb
-    new = bufs.out if dual else (lambda n, dtype=torch.float32: torch.full((n,), float('nan'), device=dev).view(dtype)[:n])
+    new = bufs.out
     dza, dzb = new(rows * c), new(rows * c)
     grads = [new(c) if g is not None else None for g in (ga, ga, gb, gb)]
     amax_a, amax_b = _amax_buf(lib, dev), _amax_buf(lib, dev)
@@ -153,9 +153,10 @@ def _run_case(cuda, rows, c, nparts, kind, affine, seed):
     dy = (torch.randn(rows, c, generator=gen) + 0.25).to(cuda)
     za, zb = za.to(cuda), zb.to(cuda)
     what = (rows, c, nparts, kind, 'affine' if affine else 'plain')
-    bufs = Bufs(cuda)
-    ref = _forward_pair(lib, cuda, za, zb, pa, pb, reca, recb, rm0, rv0, False, None)
+    bufs, ref_bufs = Bufs(cuda), Bufs(cuda)
+    ref = _forward_pair(lib, cuda, za, zb, pa, pb, reca, recb, rm0, rv0, False, ref_bufs)
     got = _forward_pair(lib, cuda, za, zb, pa, pb, reca, recb, rm0, rv0, True, bufs)
+    ref_bufs.check(what + ('forward', 'two-call path'))
     bufs.check(what + ('forward',))
     _same_bits(got, ref, what + ('forward',))
     share = (ref['y'] > 0).float().mean().item()
@@ -163,9 +164,10 @@ def _run_case(cuda, rows, c, nparts, kind, affine, seed):
     for pack_a, pack_b in itertools.product((False, True), repeat=2):
         fused = lib.evk_bn_bwd_dual_fused(PACK_DX if pack_a else 0, PACK_DX if pack_b else 0)
         assert fused == (0 if (pack_a and not pack_b) else 1), (pack_a, pack_b, fused)
-        bufs = Bufs(cuda)
-        ref_b = _backward_pair(lib, cuda, dy, za, zb, pa, pb, ref, pack_a, pack_b, False, None)
+        bufs, ref_bufs = Bufs(cuda), Bufs(cuda)
+        ref_b = _backward_pair(lib, cuda, dy, za, zb, pa, pb, ref, pack_a, pack_b, False, ref_bufs)
         got_b = _backward_pair(lib, cuda, dy, za, zb, pa, pb, got, pack_a, pack_b, True, bufs)
+        ref_bufs.check(what + ('backward', pack_a, pack_b, 'two-call path'))
         bufs.check(what + ('backward', pack_a, pack_b))
         _same_bits(got_b, ref_b, what + ('backward', 'packed' if pack_a else 'fp32', 'packed' if pack_b else 'fp32',
                                          'two-map' if fused else 'two-call inside'))

@@ -67,6 +67,45 @@ def test_forward_bits_are_the_sign_of_the_output_and_backward_takes_them(cuda, r
     assert torch.equal(outs[0][1], dy * (y > 0))
 
 
+@pytest.mark.parametrize('rows,c,past_end', [(3, 4, True), (65, 4, True), (257, 8, True), (64, 16, False)])
+def test_forward_bits_stay_inside_a_buffer_of_exactly_the_size_asked_for(cuda, rows, c, past_end):
+    """The forward apply pass runs ceil(n4 / 256) workgroups of four waves over n4 16-byte elements, and evk_relu_bits_bytes
+    asks for ceil(n4 / 64) chunks of 32 bytes: where n4 % 256 lies in 1..192 the last workgroup has waves wholly past the
+    end, which own no chunk and must store none (n4 = 3, 65, 514; n4 = 256 is the control without such a wave).  y, the
+    bits and the saved statistics sit in sentinel-guarded allocations of exactly their size."""
+    from ever_amd import _C
+    from tests.guard_common import guarded, guards_intact
+    lib = _C.load()
+    n4 = rows * c // 4
+    assert (1 <= n4 % 256 <= 192) if past_end else (n4 % 256 == 0), ('the case no longer reaches its edge', n4)
+    st = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator().manual_seed(rows + c)
+    x = torch.randn(rows, c, generator=g).to(cuda)
+    res = torch.randn(rows, c, generator=g).to(cuda)
+    gamma, beta = (torch.rand(c, generator=g) + 0.5).to(cuda), (0.1 * torch.randn(c, generator=g)).to(cuda)
+    parts = torch.stack([torch.full((c,), float(rows)), x.mean(0).cpu(), ((x - x.mean(0)) ** 2).sum(0).cpu()]).to(cuda).contiguous()
+    wsb = lib.evk_bn_workspace_bytes(rows, c)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=cuda)
+    nwords = lib.evk_relu_bits_bytes(rows * c) // 4
+    assert nwords == -(-n4 // 64) * 8
+    sizes = dict(y=rows * c, bits=nwords, save_mean=c, save_invstd=c)
+    bufs = {k: guarded(n, cuda) for k, n in sizes.items()}       # NaN inside, the sentinel around
+    y, bits, mean, invstd = (bufs[k][1] for k in ('y', 'bits', 'save_mean', 'save_invstd'))
+    _C.call('evk_bn_fwd_train_parts_bits', x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), None, None, 0.1, 1e-5,
+            y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), rows, c, 1, parts.data_ptr(), 1, ws.data_ptr(), wsb, None,
+            bits.data_ptr(), st)
+    torch.cuda.synchronize()
+    for k, (whole, _) in bufs.items():
+        assert guards_intact(whole, sizes[k]), ('a store beside', k, rows, c)
+    for k in ('y', 'save_mean', 'save_invstd'):
+        assert not torch.isnan(bufs[k][1]).any(), (k, 'holds an element nobody wrote', rows, c)
+    words = bits.view(torch.int32)
+    nan_word = torch.tensor(float('nan')).view(torch.int32).item()
+    assert not (words == nan_word).any(), ('a word of the bits nobody wrote', rows, c)
+    assert np.array_equal(_unpack_bits(words, n4), (y > 0).cpu().numpy().reshape(n4, 4))
+    assert 0 < int((y > 0).sum()) < y.numel(), 'the ReLU must cut some elements and pass others'
+
+
 def _grads(cuda, meta, bits, lazy):
     from ever_amd.hip import functional as F
     from oracle import portable
