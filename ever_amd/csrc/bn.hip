@@ -917,7 +917,7 @@ extern "C" int evk_bn_bwd_dual(const float* dy, const float* za, const float* zb
   return check_launch("bn_bwd_apply_dual");
 }
 
-// ---- BatchNorm around a fused consumer (FS-Relation, pointwise.hip: relation_bn_*): the statistics records of the
+// ---- BatchNorm around a fused consumer (FS-Relation, relation.hip: relation_*<BN>): the statistics records of the
 // producing convolution are merged into (mean, invstd, scale, shift) WITHOUT an apply pass — the consumer applies scale /
 // shift / ReLU while it reads z — and the backward takes per-workgroup partial sums that the consumer's backward formed
 // while it had g and z in registers, instead of a reduce pass of its own.

@@ -141,7 +141,7 @@ __device__ __forceinline__ void commit_absmax(uint32_t* __restrict__ slots, uint
   if ((threadIdx.x & 63) == 0 && m) atomicMax(&slots[(blockIdx.x & 63) * 32], m);
 }
 
-// Grid of the streaming kernels (csrc/pointwise.hip, csrc/hr_fuse.hip): one element per thread (their grid-stride loops then run once): resident workgroups sweep one contiguous
+// Grid of the streaming kernels (stream_common.hpp: launch_elems; csrc/hr_fuse.hip): one element per thread (their grid-stride loops then run once): resident workgroups sweep one contiguous
 // window of HBM in dispatch order, 6.1 TB/s for 1R+1W on 268 MB against 5.1 for 4096 grid-striding workgroups
 // (tools/probes/copy_patterns.hip).
 static inline int grid_for(size_t n, int per_block = 256, int cap = 1 << 24) {

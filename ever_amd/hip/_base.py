@@ -191,6 +191,38 @@ def _is_packed(t):
     return hit is not None and hit[0] == t._version and hit[1] == t.data_ptr()
 
 
+def _dx_scale(dev, want):
+    """(scale buffer, packed) of a gradient that is its producing convolution's dy and — where that convolution said so in
+    forward (`want`) — nothing else: written packed under a scale bounded before the apply pass (EVK_BN_PACK_DX)"""
+    pack = want and _f16x2()
+    abits = _amax_zeroed(dev) if pack else _amax_out(dev)
+    return abits, bool(pack and abits is not None)
+
+
+def _hand_scale(t, abits, packed):
+    """t goes on as packed words under the scale in abits, or as fp32 with its max|t| there"""
+    if packed:
+        _mark_packed(t, abits)
+    elif abits is not None:
+        _note_amax(t, abits)
+    return t
+
+
+def _take_handoff(y):
+    """a forward pass left (scale buffer, packed) of y in _AMAX_HANDOFF: y is the next convolution's operand"""
+    if _AMAX_HANDOFF[0] is not None:
+        _hand_scale(y, *_AMAX_HANDOFF[0])
+        _AMAX_HANDOFF[0] = None
+    return y
+
+
+def _affine_grads(weight, c, dev):
+    """(dgamma, dbeta) to write into, or (None, None) for a BatchNorm without affine parameters"""
+    if weight is None:
+        return None, None
+    return torch.empty((c,), device=dev, dtype=torch.float32), torch.empty((c,), device=dev, dtype=torch.float32)
+
+
 # ReLU bits (include/ever_hip.h: evk_bn_fwd_train_parts_bits): the BatchNorm + add + ReLU that ends a residual block keeps one
 # bit per output element and its backward reads those instead of the output tensor; with `lazy_res` the identity branch's
 # gradient is not written either — the unmasked incoming gradient travels on with the bits (`_evk_relu_bits` on a view of

@@ -12,45 +12,13 @@ from .. import _C
 from . import timing, weight_planes
 from .workspace import workspace
 from ._base import (  # noqa: F401
-    HipPathError, _AMAX_HANDOFF, _LAZY_RES, _PACKED, _RELU_BITS, _amax_out, _amax_zeroed, _f16x2, _inherit_amax,
-    _lazy_bits, _mark_packed, _note_amax, _ptr, _require_cuda, _stream, _timed_call, as_nhwc, empty_nhwc, is_nhwc,
-    materialize_lazy, observers_active, relu_bits_stats,
+    HipPathError, _AMAX_HANDOFF, _LAZY_RES, _PACKED, _RELU_BITS, _affine_grads, _amax_out, _amax_zeroed, _dx_scale, _f16x2,
+    _hand_scale, _inherit_amax, _lazy_bits, _mark_packed, _note_amax, _ptr, _require_cuda, _stream, _take_handoff, _timed_call,
+    as_nhwc, empty_nhwc, is_nhwc, materialize_lazy, observers_active, relu_bits_stats,
 )
 
 
 # ------------------------------------------------------------------------------------ batch norm
-def _dx_scale(dev, want):
-    """(scale buffer, packed) of a gradient that is its producing convolution's dy and — where that convolution said so in
-    forward (`want`) — nothing else: written packed under a scale bounded before the apply pass (EVK_BN_PACK_DX)"""
-    pack = want and _f16x2()
-    abits = _amax_zeroed(dev) if pack else _amax_out(dev)
-    return abits, bool(pack and abits is not None)
-
-
-def _hand_scale(t, abits, packed):
-    """t goes on as packed words under the scale in abits, or as fp32 with its max|t| there"""
-    if packed:
-        _mark_packed(t, abits)
-    elif abits is not None:
-        _note_amax(t, abits)
-    return t
-
-
-def _take_handoff(y):
-    """a forward pass left (scale buffer, packed) of y in _AMAX_HANDOFF: y is the next convolution's operand"""
-    if _AMAX_HANDOFF[0] is not None:
-        _hand_scale(y, *_AMAX_HANDOFF[0])
-        _AMAX_HANDOFF[0] = None
-    return y
-
-
-def _affine_grads(weight, c, dev):
-    """(dgamma, dbeta) to write into, or (None, None) for a BatchNorm without affine parameters"""
-    if weight is None:
-        return None, None
-    return torch.empty((c,), device=dev, dtype=torch.float32), torch.empty((c,), device=dev, dtype=torch.float32)
-
-
 class _BatchNormActFn(Function):
     """BatchNorm2d (+ residual add) (+ ReLU) in one pass.
 

@@ -12,8 +12,8 @@ from .. import _C
 from . import timing, weight_planes
 from .workspace import workspace
 from ._base import (  # noqa: F401
-    HipPathError, _AMAX_HANDOFF, _amax_out, _amax_zeroed, _conv_out, _f16x2, _inherit_amax, _mark_packed, _note_amax, _ptr,
-    _require_cuda, _same_shape_fake, _stream, _timed_call, as_nhwc, empty_nhwc,
+    HipPathError, _AMAX_HANDOFF, _affine_grads, _amax_zeroed, _conv_out, _dx_scale, _hand_scale, _inherit_amax, _note_amax, _ptr,
+    _require_cuda, _same_shape_fake, _stream, _take_handoff, _timed_call, as_nhwc, empty_nhwc,
 )
 from .streams import (  # noqa: F401
     _note_param_use,
@@ -313,21 +313,14 @@ class _RelationBnFn(Function):
         for k, (g, z, gamma) in enumerate(((gc, zc, wc), (gf, zf, wf))):
             sums = ws[nb * c * (1 + 4 * k):]
             maxima = ws[nb * c * (3 + 4 * k):]
-            pack = ctx.pack[k] and _f16x2()
-            abits = _amax_zeroed(dev) if pack else _amax_out(dev)
-            pack = pack and abits is not None
+            abits, pack = _dx_scale(dev, ctx.pack[k])
             dz = torch.empty_like(z)
-            dgamma = torch.empty((c,), device=dev, dtype=torch.float32) if gamma is not None else None
-            dbeta = torch.empty((c,), device=dev, dtype=torch.float32) if gamma is not None else None
+            dgamma, dbeta = _affine_grads(gamma, c, dev)
             # algorithmic bytes: read g, z, write dz
             _timed_call('bn', 12.0 * z.numel(), 'evk_bn_bwd_from_partials', g.data_ptr(), z.data_ptr(), _ptr(gamma),
                         stats[k, 0].data_ptr(), stats[k, 1].data_ptr(), sums.data_ptr(), maxima.data_ptr(), nb, dz.data_ptr(),
                         _ptr(dgamma), _ptr(dbeta), rows, c, 2 if pack else 0, 1, coef.data_ptr(), 16 * c * 4, _ptr(abits), st)
-            if pack:
-                _mark_packed(dz, abits)
-            elif abits is not None:
-                _note_amax(dz, abits)
-            grads.append((dz, dgamma, dbeta))
+            grads.append((_hand_scale(dz, abits, pack), dgamma, dbeta))
         (dzc, dgc, dbc), (dzf, dgf, dbf) = grads
         return dscene, dzc, dzf, dgc, dbc, dgf, dbf, None, None, None, None, None
 
@@ -350,12 +343,7 @@ def fs_relation_bn(scene, zc, zf, bn_c, bn_f):
     out = _RelationBnFn.apply(scene, zc, zf, bn_c.weight, bn_c.bias, bn_f.weight, bn_f.bias, stat(bn_c, 'running_mean'),
                               stat(bn_c, 'running_var'), stat(bn_f, 'running_mean'), stat(bn_f, 'running_var'),
                               (pc, pf, bn_c.momentum, bn_c.eps, bn_f.momentum, bn_f.eps))
-    if _AMAX_HANDOFF[0] is not None:
-        abits, _ = _AMAX_HANDOFF[0]
-        if abits is not None:
-            _note_amax(out, abits)
-        _AMAX_HANDOFF[0] = None
-    return out
+    return _take_handoff(out)
 
 
 class _BnReluDotFn(Function):
@@ -395,12 +383,9 @@ class _BnReluDotFn(Function):
         lib = _C.load()
         ws_bytes = lib.evk_bn_relu_dot_workspace_bytes(rows, c, k)
         ws = workspace(dev, ws_bytes)
-        pack = ctx.pack and _f16x2()
-        abits = _amax_zeroed(dev) if pack else _amax_out(dev)
-        pack = pack and abits is not None
+        abits, pack = _dx_scale(dev, ctx.pack)
         dz = torch.empty_like(z)
-        dgamma = torch.empty((c,), device=dev, dtype=torch.float32) if gamma is not None else None
-        dbeta = torch.empty((c,), device=dev, dtype=torch.float32) if gamma is not None else None
+        dgamma, dbeta = _affine_grads(gamma, c, dev)
         # (OHWI memory = [k][c] for a 1x1 kernel, presented with exactly the parameter's strides: the size-1 dims make the
         # stride tuple ambiguous, and a gradient in "another layout" costs AccumulateGrad / the bucket pack a copy)
         dw = torch.empty_strided(w.shape, w.stride(), device=dev, dtype=torch.float32) if (
@@ -411,11 +396,7 @@ class _BnReluDotFn(Function):
         _timed_call('bn', 12.0 * z.numel(), 'evk_bn_relu_dot_bwd', dl.data_ptr(), z.data_ptr(), stats[2].data_ptr(), _ptr(gamma),
                     stats[0].data_ptr(), stats[1].data_ptr(), w2.data_ptr(), dz.data_ptr(), _ptr(dgamma), _ptr(dbeta),
                     dw.data_ptr(), _ptr(dbias), rows, c, k, 2 if pack else 0, ws.data_ptr(), ws_bytes, _ptr(abits), st)
-        if pack:
-            _mark_packed(dz, abits)
-        elif abits is not None:
-            _note_amax(dz, abits)
-        return dz, dgamma, dbeta, dw, dbias, None, None, None
+        return _hand_scale(dz, abits, pack), dgamma, dbeta, dw, dbias, None, None, None
 
 
 def bn_relu_dot(z, bn, conv):

@@ -8,7 +8,7 @@ import numpy as np
 
 SCALAR, VEC, TILE32, TILE64, WAVE = range(5)
 KERNEL_NAMES = ('scalar element', 'vec element', 'tile-32', 'tile-64', 'wave')
-TILE_R, TILE_C = 4, 16          # output pixels per workgroup of the tile kernels (csrc/pointwise.hip: kTileR, kTileC)
+TILE_R, TILE_C = 4, 16          # output pixels per workgroup of the tile kernels (csrc/resample.hip: kTileR, kTileC)
 WAVE_CANDIDATES = 16            # candidate slots per axis of the wave kernel (lane & 15)
 LDS_BYTES = 64 * 1024
 

@@ -1,4 +1,4 @@
-"""The resampling and pooling kernels of csrc/pointwise.hip at their dispatch edges: bilinear (four forward kernels, three
+"""The resampling and pooling kernels of csrc/resample.hip and csrc/pool.hip at their dispatch edges: bilinear (four forward kernels, three
 backward kernels, dense and channel-slice calls), MaxPool 3x3 s2, the x2 sub-sampling of LastLevelMaxPool, nearest x2 + add and
 the global average pool.  Every kernel is called through the C ABI into NaN-filled, sentinel-guarded outputs
 (tests/guard_common.py): nothing outside the result may be written, nothing inside it may stay NaN.
@@ -7,7 +7,7 @@ Bilinear cases come from tests/resample_common.py; tests/test_resample_plan_cpu.
 Reference: F.interpolate(x.double(), size, mode='bilinear', align_corners=True) on the CPU and its autograd.  Tolerance: nothing
 fixed in advance — aten's own fp32 CPU result is measured against the same fp64 reference, and the kernel may err at most twice
 as much plus 4 ulp of the largest |reference| (both sides round scale * o once in float; an equal-size case has a yardstick of 0,
-hence the floor).  The factor two is the margin of test_ops_gpu.py::test_conv_split_matches_fp64_as_well_as_fp32_mfma.
+hence the floor; tests/yardstick_common.py).
 
 Pools and selections are compared bit for bit with aten on the CPU (integer-valued gradients make their sums exact)."""
 import functools
@@ -19,6 +19,7 @@ import torch.nn.functional as TF
 
 from tests.guard_common import guarded, guards_intact
 from tests.resample_common import CASES, SLICE_CASES, case_id
+from tests.yardstick_common import as_close_as_aten as _as_close_as_aten
 
 pytestmark = pytest.mark.gpu
 
@@ -53,21 +54,6 @@ def _same_bits(got, ref, what):
     bad = _bits(got) != _bits(ref)
     assert not bool(bad.any()), (f'{what}: {int(bad.sum())} of {bad.numel()} elements differ in their bits, first at '
                                  f'{tuple(int(v) for v in bad.nonzero()[0])}: {got[bad][0].item()!r} vs {ref[bad][0].item()!r}')
-
-
-def _ulp(v):
-    return float(np.spacing(np.float32(abs(v))))
-
-
-def _as_close_as_aten(got, ref64, ref32, what, ulps=4):
-    """max |got - ref64| <= 2 max |aten fp32 - ref64| + ulps ulp(max |ref64|); returns error / yardstick for the record"""
-    assert got.shape == ref64.shape, (what, tuple(got.shape), tuple(ref64.shape))
-    yard = (ref32.double() - ref64).abs().max().item()
-    err = (got.double() - ref64).abs().max().item()
-    floor = ulps * _ulp(ref64.abs().max().item())
-    print(f'{what}: kernel err {err:.3e}, aten fp32 err {yard:.3e}, ratio {err / yard if yard else float("nan"):.3f}, '
-          f'bound {2 * yard + floor:.3e} (used {err / (2 * yard + floor):.3f})')
-    assert err <= 2 * yard + floor, f'{what}: err {err:.3e} > 2 * {yard:.3e} + {floor:.3e}'
 
 
 # ------------------------------------------------------------------------------------------------ bilinear

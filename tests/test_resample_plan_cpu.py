@@ -1,4 +1,4 @@
-"""The bilinear resampling plan (csrc/pointwise.hip: bilinear_plan), asked of the library on the host through
+"""The bilinear resampling plan (csrc/resample.hip: bilinear_plan), asked of the library on the host through
 evk_upsample_bilinear_plan — the function bilinear_fwd_launch and bilinear_bwd_launch call, no Python copy of its predicates.
 
 What the kernels take on trust from that plan, checked here with aten's coordinate formula in numpy float32 on the plan's own
