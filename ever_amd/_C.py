@@ -150,6 +150,9 @@ SIGNATURES = {
     'evk_d4_merge': (c_int, [P, P, c_i32, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_d4_plan': (c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
     'evk_d4_force_kernel': (c_int, [c_i32]),
+    'evk_augment_batch': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P, P, c_i32, c_i32, c_i32, c_i32, P, P, P]),
+    'evk_augment_plan': (c_int, [c_i32] * 12 + [C.POINTER(c_i32)]),
+    'evk_augment_force_kernel': (c_int, [c_i32]),
     'evk_gap_fwd': (c_int, [P, P, c_i32, c_i32, c_i32, P]),
     'evk_gap_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, P]),
     'evk_relation_fwd': (c_int, [P, P, P, P, P, c_i32, c_i32, c_i32, P]),

@@ -21,7 +21,7 @@ from .core.logger import info  # noqa: E402
 from .core.to import to_device, to_tensor  # noqa: E402
 from .interface import (Callback, ConfigurableMixin, ERDataLoader, ERDataset, ERModule,  # noqa: E402
                         LearningRateBase, MultiTransform, Transform)
-from . import api, data, magic, metric, module, opt, trainer  # noqa: E402,F401
+from . import api, data, magic, metric, module, opt, preprocess, trainer  # noqa: E402,F401
 from .core.launcher import Launcher  # noqa: E402
 from .magic.transform.tta import *  # noqa: E402,F401,F403  (tta, TestTimeAugmentation: at the top level, as the reference)
 

@@ -13,7 +13,7 @@ from torch.autograd.function import once_differentiable
 from . import oplib
 from ._base import HipPathError, _is_packed, _ptr, _require_cuda, _stream, _timed_call, empty_nhwc, is_nhwc, materialize_lazy
 
-__all__ = ['d4', 'd4_mean', 'd4_inverse', 'd4_out_hw', 'd4_stats', 'D4_IDENTITY', 'D4_TRANSPOSE', 'D4_VFLIP', 'D4_HFLIP',
+__all__ = ['d4', 'd4_mean', 'd4_inverse', 'd4_compose', 'd4_out_hw', 'd4_stats', 'D4_IDENTITY', 'D4_TRANSPOSE', 'D4_VFLIP', 'D4_HFLIP',
            'D4_ROT90']
 
 D4_IDENTITY, D4_TRANSPOSE, D4_VFLIP, D4_HFLIP = 0, 1, 2, 4       # flip(x, [2]) reverses rows, flip(x, [3]) columns
@@ -25,6 +25,15 @@ d4_stats = {'apply': 0, 'mean': 0, 'mean_terms': 0, 'mean_launches': 0}     # te
 def d4_inverse(op):
     """the op that undoes `op`: the two quarter turns undo each other, every other element is an involution"""
     return {3: 5, 5: 3}.get(op, op)
+
+
+def d4_compose(a, b):
+    """the one op that applies `a`, then `b`.  With an op written F(rows, cols) . T^swap (transpose first, then flip), moving
+    b's transpose left past a's flips exchanges them (T . F(r, c) = F(c, r) . T); flips commute and cancel in pairs."""
+    fr, fc = (a >> 1) & 1, (a >> 2) & 1
+    if b & 1:
+        fr, fc = fc, fr
+    return ((a ^ b) & 1) | ((fr ^ (b >> 1) & 1) << 1) | ((fc ^ (b >> 2) & 1) << 2)
 
 
 def d4_out_hw(h, w, op):

@@ -577,6 +577,40 @@ int evk_d4_plan(int32_t N, int32_t Hi, int32_t Wi, int32_t C, int32_t op, int32_
  * the rule everywhere.  Returns the previous setting (-1: none). */
 int evk_d4_force_kernel(int32_t kernel);
 
+/* Augmentation and input preparation of a whole batch in one launch — preprocess/thsegm.py, thcomm.py: THRandomRotate90k ->
+ * THRandomHorizontalFlip -> THRandomVerticalFlip -> THRandomCrop((crop_h, crop_w)) -> THChannelFirst2 -> THMeanStdNormalize2
+ * -> THDivisiblePad per image, then torch.stack (csrc/augment.hip).  The random draws are the caller's: sample i comes with
+ * one op (the 3 bits above) and one crop origin.
+ * Sample i is a dense source S [Hs,Ws,C] (uint8, or fp32 when src_f32) at any byte address and, unless mask_mode is 0, a
+ * dense label map [Hs,Ws].  T = d4(S, op) has (Ht, Wt) = swap ? (Ws, Hs) : (Hs, Ws).  For pixel (r, c) of the [Ho,Wo] output:
+ *   r < crop_h and c < crop_w: (a, b) = (y0 + r, x0 + c); raw = a < Ht and b < Wt ? T[a,b,:] : 0 and the label likewise (the
+ *     zero pad inside THRandomCrop); value = (float(raw) - mean[k]) / std[k] — one rounded subtraction, one correctly rounded
+ *     division, no reciprocal, no fma — or float(raw) when mean and std are NULL
+ *   else: value +0.0f, label mask_pad_value.
+ * out: [N,Ho,Wo,C] (nchw == 0) or [N,C,Ho,Wo] fp32.  mask_mode 0: no labels (the mask words and out_mask are ignored);
+ * 1: uint8 -> uint8; 2: uint8 -> int64 (zero-extended); 3: int64 -> int64; out_mask: [N,Ho,Wo].
+ * `records` (HOST, read during the call) and `table` (DEVICE, read by the kernel; the caller uploads it in stream order)
+ * hold the same N records of 8 int64: { image address, mask address, Hs, Ws, op, y0, x0, 0 }.  mean / std: C fp32 in DEVICE
+ * memory, both or neither.  No atomics: every element has one writer, two runs give the same bits.
+ * Refused before any launch: -1 for a null table, output or image, mean without std, a crop larger than the output, an op
+ * outside 0..7, an origin outside 0 <= y0 <= max(Ht, crop_h) - crop_h (and the same for x0); -2 for C > 64, a source of
+ * 2^31 elements or more, an output of 2^31 elements or more, N > 65535. */
+int evk_augment_batch(const int64_t* records, const int64_t* table, int32_t N, int32_t C, int32_t crop_h, int32_t crop_w,
+                      int32_t Ho, int32_t Wo, const float* mean, const float* std, int32_t mask_pad_value, int32_t nchw,
+                      int32_t src_f32, int32_t mask_mode, float* out, void* out_mask, void* stream);
+/* Host only, no launch: the checks evk_augment_batch makes on one sample (same return codes) and the kernel form its
+ * (C, dtype, op, layout) takes.  out[6] = { kernel, tile edge T in pixels, LDS row stride in floats, LDS bytes, elements per
+ * thread, 16-byte stores }.  kernel 0: direct, four consecutive output elements per thread and one 16-byte store when the last
+ * number is 1 (Ho*Wo % 4 == 0; the launcher falls back to an element per thread for an output off the 16-byte grid); 1: LDS tile
+ * (swap ops; numbers two to five are 0 otherwise).
+ * A launch takes the tile kernel when the plan of any of its samples does; samples without a swap op read directly in it. */
+int evk_augment_plan(int32_t Hs, int32_t Ws, int32_t C, int32_t op, int32_t y0, int32_t x0, int32_t crop_h, int32_t crop_w,
+                     int32_t Ho, int32_t Wo, int32_t src_f32, int32_t nchw, int32_t* out);
+/* For measurements and tests only (tools/bench_augment.py, tests/test_augment_gpu.py); the package never calls it.  From now
+ * on, in this process, the plan names `kernel` (0, 1, or 2: direct with 4-byte stores only) wherever it is legal (1 needs a swap
+ * op) and follows its own rule elsewhere; any other value, -1 by custom, restores the rule.  Returns the previous setting. */
+int evk_augment_force_kernel(int32_t kernel);
+
 /* F.adaptive_avg_pool2d(x, 1) — fs_relation.py:177. x: [N,HW,C] -> y: [N,C]. */
 int evk_gap_fwd(const float* x, float* y, int32_t N, int32_t HW, int32_t C, void* stream);
 int evk_gap_bwd(const float* dy, float* dx, int32_t N, int32_t HW, int32_t C, void* stream);
