@@ -106,6 +106,7 @@ SIGNATURES = {
     'evk_bn_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_i64, c_i32, c_u32, c_i32, P, c_size_t, P, P]),
     'evk_stream_fork': (c_int, [P, P]),
     'evk_streams_overlap': (c_int, [P, P, c_i32, P]),
+    'evk_bn_relu_dot_plan': (c_int, [c_i64, c_i32, c_i32, C.POINTER(c_i32)]),
     'evk_bn_relu_dot_fwd': (c_int, [P, P, P, P, P, c_i64, c_i32, c_i32, P]),
     'evk_bn_relu_dot_workspace_bytes': (c_size_t, [c_i64, c_i32, c_i32]),
     'evk_bn_relu_dot_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_i64, c_i32, c_i32, c_u32, P, c_size_t, P, P]),

@@ -252,6 +252,23 @@ static bool dot_variant(int C, int K, int& nch, int& kt) {
   kt = K <= 1 ? 1 : (K <= 4 ? 4 : 16);
   return nch == 1 || ((nch == 2 || nch == 4) && kt <= 4);
 }
+// What both launchers and evk_bn_relu_dot_plan derive from (rows, C, K): the grid, the pixel range of a workgroup, the
+// instantiation and the dynamic LDS of the backward's partial kernel ([4 waves][4 + K][C] floats; its static sdb[4][16]
+// comes on top).  bwd: also hold the shape to what the backward can run (the forward uses no LDS).
+struct DotPlan {
+  int nblk, nch, kt;
+  size_t pix_per_blk, lds;
+};
+static int dot_plan(const char* what, int64_t rows, int32_t C, int32_t K, bool bwd, DotPlan& p) {
+  EVK_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && (!bwd || C <= 1024) && K > 0 && K <= kDotMaxK, EVK_E_UNSUPPORTED,
+              "%s: rows=%lld C=%d K=%d", what, (long long)rows, C, K);
+  EVK_REQUIRE(dot_variant(C, K, p.nch, p.kt), EVK_E_UNSUPPORTED, "%s: C=%d K=%d has no instantiation", what, C, K);
+  p.lds = (size_t)4 * (4 + K) * C * sizeof(float);
+  EVK_REQUIRE(!bwd || p.lds <= 64 * 1024, EVK_E_UNSUPPORTED, "%s: C=%d K=%d do not fit the LDS", what, C, K);
+  p.nblk = dot_blocks((size_t)rows);
+  p.pix_per_blk = ((size_t)rows + p.nblk - 1) / p.nblk;
+  return EVK_OK;
+}
 // LAUNCH(NCH, KT) for the pair dot_variant chose
 #define EVK_DOT_DISPATCH(nch, kt, LAUNCH)                                   \
   do {                                                                      \
@@ -270,11 +287,11 @@ using namespace evk;
 extern "C" int evk_bn_relu_dot_fwd(const float* z, const float* scale_shift, const float* w, const float* bias, float* out,
                                    int64_t rows, int32_t C, int32_t K, void* stream) {
   EVK_REQUIRE(z && scale_shift && w && out, EVK_E_INVALID, "bn_relu_dot_fwd: null pointer");
-  EVK_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && K > 0 && K <= kDotMaxK, EVK_E_UNSUPPORTED, "bn_relu_dot_fwd: C=%d K=%d", C, K);
-  int nch, kt;
-  EVK_REQUIRE(dot_variant(C, K, nch, kt), EVK_E_UNSUPPORTED, "bn_relu_dot_fwd: C=%d K=%d has no instantiation", C, K);
-  const int nb = dot_blocks((size_t)rows);
-  const size_t ppb = ((size_t)rows + nb - 1) / nb;
+  DotPlan pl;
+  int rc = dot_plan("bn_relu_dot_fwd", rows, C, K, false, pl);
+  if (rc) return rc;
+  const int nb = pl.nblk, nch = pl.nch, kt = pl.kt;
+  const size_t ppb = pl.pix_per_blk;
   hipStream_t st = (hipStream_t)stream;
 #define EVK_DOT_FWD(NCH, KT)                                                                                              \
   hipLaunchKernelGGL((bn_relu_dot_fwd_kernel<NCH, KT>), dim3(nb), dim3(256), 0, st, z, scale_shift, w, bias, out, (size_t)rows, \
@@ -282,6 +299,23 @@ extern "C" int evk_bn_relu_dot_fwd(const float* z, const float* scale_shift, con
   EVK_DOT_DISPATCH(nch, kt, EVK_DOT_FWD);
 #undef EVK_DOT_FWD
   return check_launch("bn_relu_dot_fwd");
+}
+// Host only (no launch): what evk_bn_relu_dot_fwd / _bwd do with a [rows][C] map and K classes, from the function both call.
+// out = {workgroups, pixels per workgroup, NCH, KT, dynamic LDS bytes of the backward's partial kernel}.  Refuses what the
+// backward refuses, with its codes.
+extern "C" int evk_bn_relu_dot_plan(int64_t rows, int32_t C, int32_t K, int32_t* out) {
+  EVK_REQUIRE(out, EVK_E_INVALID, "bn_relu_dot_plan: null pointer");
+  DotPlan pl;
+  int rc = dot_plan("bn_relu_dot_plan", rows, C, K, true, pl);
+  if (rc) return rc;
+  EVK_REQUIRE(pl.pix_per_blk <= 0x7fffffffULL, EVK_E_UNSUPPORTED, "bn_relu_dot_plan: rows=%lld do not fit the answer",
+              (long long)rows);
+  out[0] = pl.nblk;
+  out[1] = (int32_t)pl.pix_per_blk;
+  out[2] = pl.nch;
+  out[3] = pl.kt;
+  out[4] = (int32_t)pl.lds;
+  return EVK_OK;
 }
 extern "C" size_t evk_bn_relu_dot_workspace_bytes(int64_t rows, int32_t C, int32_t K) {
   if (rows <= 0 || C <= 0 || K <= 0) return 0;
@@ -294,30 +328,28 @@ extern "C" int evk_bn_relu_dot_bwd(const float* dl, const float* z, const float*
                                    float* dbeta, float* dw, float* dbias, int64_t rows, int32_t C, int32_t K, uint32_t flags,
                                    void* workspace, size_t workspace_bytes, uint32_t* dx_absmax, void* stream) {
   EVK_REQUIRE(dl && z && scale_shift && save_mean && save_invstd && w && dz && dw, EVK_E_INVALID, "bn_relu_dot_bwd: null pointer");
-  EVK_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && C <= 1024 && K > 0 && K <= kDotMaxK, EVK_E_UNSUPPORTED,
-              "bn_relu_dot_bwd: C=%d K=%d", C, K);
+  DotPlan pl;
+  int rc = dot_plan("bn_relu_dot_bwd", rows, C, K, true, pl);
+  if (rc) return rc;
   EVK_REQUIRE(workspace && workspace_bytes >= evk_bn_relu_dot_workspace_bytes(rows, C, K), EVK_E_WORKSPACE,
-              "bn_relu_dot_bwd: workspace too small");
+              "bn_relu_dot_bwd: workspace too small for rows=%lld C=%d K=%d", (long long)rows, C, K);
   const bool pack = (flags & EVK_BN_PACK_DX) != 0;
-  EVK_REQUIRE(!pack || dx_absmax, EVK_E_INVALID, "bn_relu_dot_bwd: EVK_BN_PACK_DX needs dx_absmax (slots zero on entry)");
+  EVK_REQUIRE(!pack || dx_absmax, EVK_E_INVALID,
+              "bn_relu_dot_bwd: EVK_BN_PACK_DX needs dx_absmax (slots zero on entry), C=%d K=%d", C, K);
   hipStream_t st = (hipStream_t)stream;
-  const int nb = dot_blocks((size_t)rows);
-  const size_t ppb = ((size_t)rows + nb - 1) / nb;
+  const int nb = pl.nblk, nch = pl.nch, kt = pl.kt;
+  const size_t ppb = pl.pix_per_blk, lds = pl.lds;
   float* bnp = (float*)workspace;
   float* bnm = bnp + (size_t)nb * 2 * C;
   float* dwp = bnm + (size_t)nb * 2 * C;
   float* dbp = dwp + (size_t)nb * K * C;
   float* coef = dbp + (size_t)nb * K;
-  const size_t lds = (size_t)4 * (4 + K) * C * sizeof(float);
-  EVK_REQUIRE(lds <= 64 * 1024, EVK_E_UNSUPPORTED, "bn_relu_dot_bwd: C=%d K=%d do not fit the LDS", C, K);
-  int nch, kt;
-  EVK_REQUIRE(dot_variant(C, K, nch, kt), EVK_E_UNSUPPORTED, "bn_relu_dot_bwd: C=%d K=%d has no instantiation", C, K);
 #define EVK_DOT_PARTIAL(NCH, KT)                                                                                          \
   hipLaunchKernelGGL((bn_relu_dot_bwd_partial_kernel<NCH, KT>), dim3(nb), dim3(256), lds, st, dl, z, scale_shift, save_mean, \
                      save_invstd, w, bnp, bnm, dwp, dbp, (size_t)rows, C, K, ppb)
   EVK_DOT_DISPATCH(nch, kt, EVK_DOT_PARTIAL);
 #undef EVK_DOT_PARTIAL
-  int rc = check_launch("bn_relu_dot_bwd_partial");
+  rc = check_launch("bn_relu_dot_bwd_partial");
   if (rc) return rc;
   launch_bn_bwd_final(st, bnp, nb, C, rows, gamma, save_invstd, dgamma, dbeta, coef, 1, dx_absmax, pack ? bnm : nullptr);
   rc = check_launch("bn_bwd_final");

@@ -399,13 +399,25 @@ class _BnReluDotFn(Function):
         return _hand_scale(dz, abits, pack), dgamma, dbeta, dw, dbias, None, None, None
 
 
+def bn_relu_dot_admits(c, k, kernel_shape=(1, 1)):
+    """Does the fused BatchNorm + ReLU + classifier pass take C = c channels, k classes and this kernel?  The mirror of
+    csrc/bn_dot.hip: dot_plan (evk_bn_relu_dot_plan answers the same on the host; tests/test_bn_dot_plan_cpu.py holds the two
+    together): 1 .. 16 classes, 16-byte channel chunks, more than 4 classes only where a lane owns one chunk (C <= 256: the
+    registers), and the backward's [4 waves][4 + k][c] floats of LDS within 64 KiB.  (`1 <= k`: the sweep of that test found
+    the earlier form of this gate admitting a classifier without outputs, which the library refuses.  The 64 KiB count the
+    dynamic allocation; both shapes that meet it exactly, (512, 4) and (256, 12), launch with the kernel's 256 static bytes
+    on top: tests/test_bn_dot_gpu.py.)"""
+    return (tuple(kernel_shape) == (1, 1) and 1 <= k <= 16 and c > 0 and c % 4 == 0 and c <= 1024
+            and (c <= 256 or k <= 4) and 16 * (4 + k) * c <= 65536)
+
+
 def bn_relu_dot(z, bn, conv):
     """`conv(relu(bn(z)))` for a training-mode BatchNorm2d whose statistics records ride on z (`_evk_bn_parts`) and a 1x1
     convolution with at most 16 outputs, as one pass each way (see _BnReluDotFn); None when that form does not apply."""
     parts = getattr(z, '_evk_bn_parts', None)
     k, c = conv.weight.shape[0], z.shape[1]
-    if (parts is None or parts[1] <= 0 or k > 16 or c % 4 or c > 1024 or tuple(conv.weight.shape[2:]) != (1, 1)
-            or conv.weight.shape[1] != c or (c > 256 and k > 4) or 16 * (4 + k) * c > 65536):
+    if (parts is None or parts[1] <= 0 or conv.weight.shape[1] != c
+            or not bn_relu_dot_admits(c, k, conv.weight.shape[2:])):
         return None      # (the kernel's register / LDS budget: csrc/bn_dot.hip evk_bn_relu_dot_bwd)
     del z._evk_bn_parts
     weight_planes.note_running_stats_changed()

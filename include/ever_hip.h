@@ -804,7 +804,12 @@ int evk_bn_bwd_from_partials(const float* g, const float* x, const float* gamma,
  * classifier before the last upsampling): out[pix][k] = sum_c relu(bn(z))[pix][c] * w[k][c] + bias[k], K <= 16.  The
  * normalised map is never written.  scale_shift / save_mean / save_invstd from evk_bn_finalize_parts.  Backward: dl
  * [rows][K] -> dz (gradient of z; EVK_BN_PACK_DX: packed, dx_absmax zero on entry), dgamma, dbeta, dw [K][C], dbias [K];
- * it reads z twice and never forms the C-channel gradient of the normalised map. */
+ * it reads z twice and never forms the C-channel gradient of the normalised map.
+ * evk_bn_relu_dot_plan (host only, no launch) answers what both do with a [rows][C] map and K classes: out[5] = {workgroups,
+ * pixels per workgroup, NCH, KT, dynamic LDS bytes of the backward} — a lane owns NCH (1, 2, 4) 16-byte channel chunks, KT
+ * (1, 4, 16) classes are unrolled.  It returns what evk_bn_relu_dot_bwd returns for the same shape: EVK_E_UNSUPPORTED for a
+ * C / K without an instantiation or beyond the LDS (16 (4 + K) C <= 65536), EVK_E_INVALID for a null `out`. */
+int evk_bn_relu_dot_plan(int64_t rows, int32_t C, int32_t K, int32_t* out);
 int evk_bn_relu_dot_fwd(const float* z, const float* scale_shift, const float* w, const float* bias, float* out, int64_t rows,
                         int32_t C, int32_t K, void* stream);
 size_t evk_bn_relu_dot_workspace_bytes(int64_t rows, int32_t C, int32_t K);

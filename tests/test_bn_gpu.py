@@ -1,5 +1,5 @@
-"""The BatchNorm family (csrc/bn.hip, bn_pool.hip, bn_dot.hip) at its plan, channel and map-shape edges, through the C-ABI,
-against float64 computed on the CPU from the same fp32 inputs.
+"""The BatchNorm family (csrc/bn.hip, bn_pool.hip; bn_dot.hip has tests/test_bn_dot_gpu.py) at its plan, channel and map-shape
+edges, through the C-ABI, against float64 computed on the CPU from the same fp32 inputs.
 
 Shapes are picked WITH evk_bn_plan: a case names the edges it exists for (`want`) and fails with "no longer covers" when a
 retuned plan takes one away; the last test asserts the union.  Every output and the workspace hold NaN before a launch and are
@@ -20,18 +20,15 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from tests.guard_common import guarded, guards_intact
+from tests.bn_ref_common import (LEFT_OUT, NAN_BITS, U, WORST, Bufs, Stats, _amax_holds, _bwd_ref, _data, _given_stats,  # noqa: F401
+                                 _hold, _params, _ptr, _stream)
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
 EPS = float(np.float32(1e-5))
 MOM = float(np.float32(0.1))
 RELU = 1
-NAN_BITS = 0x7fc00000
-LEFT_OUT = 1e-3         # share of elements (windows) that may go without a gradient
 
-WORST = {}              # quantity -> (error / bound, where)
 RAN = {}                # test -> set of edges its cases asserted and ran
 
 
@@ -50,61 +47,7 @@ def _chains(pl):
     return n_t // 4 + 2 + 3 + (rl - 1), n_t + (rl - 1)
 
 
-class Bufs:
-    """device outputs of one case: NaN-filled, each inside its own sentinel-guarded allocation"""
-
-    def __init__(self, dev):
-        self.dev, self.all = dev, []
-
-    def out(self, n, dtype=torch.float32):
-        nf = (n * torch.empty((), dtype=dtype).element_size() + 3) // 4
-        whole, inner = guarded(nf, self.dev)
-        self.all.append((whole, nf))
-        return inner.view(dtype)[:n]
-
-    def workspace(self, lib, rows, c):
-        nbytes = lib.evk_bn_workspace_bytes(rows, c)
-        return self.out(nbytes // 4), nbytes
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        for whole, n in self.all:
-            assert guards_intact(whole, n), ('a store beside a buffer', what)
-
-
-def _amax_holds(words, out, what):
-    """the maximum over the 64 slots (a cache line apart) is max|out| bit for bit; no other word was touched"""
-    w = words.cpu().view(64, 32)
-    want = int(out.abs().max().reshape(1).cpu().view(torch.int32))
-    assert int(w[:, 0].max()) == want, ('absmax', what, hex(int(w[:, 0].max())), hex(want))
-    assert bool((w[:, 1:] == NAN_BITS).all()), ('absmax: a word between the slots', what)
-
-
-def _hold(name, got, ref, bound, what):
-    got = got.detach().cpu()
-    assert torch.isfinite(got).all(), (name, 'holds an element nobody wrote', what)
-    err = (got.double() - ref).abs()
-    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.expand_as(err).clamp_min(1e-300))
-    worst = ratio.max().item()
-    if worst > WORST.get(name, (-1.0,))[0]:
-        WORST[name] = (worst, what)
-    print(f'{str(what):44s} {name:14s} error / bound {worst:.3f}')
-    assert worst <= 1.0, (name, what, 'error / bound', worst)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 # ------------------------------------------------------------------------------------------------ float64 references
-class Stats:
-    pass
-
-
 def _stats_ref(ranks, chains):
     """float64 batch statistics of the concatenated `ranks` ([rows_r][C] fp32) and the bounds of what the statistics pass
     (pivot = first row of each rank, chain chains[r]) and the fp64 merge make of them"""
@@ -130,12 +73,6 @@ def _stats_ref(ranks, chains):
     st.e_mean = e_mean64 + U * st.mean.abs()
     st.e_var = e_m2 / n_tot
     st.e_invstd = ((st.var - st.e_var).clamp_min(0) + EPS).rsqrt() - st.invstd + U * st.invstd
-    return st
-
-
-def _given_stats(mean, invstd, e_mean, e_invstd):
-    st = Stats()
-    st.mean, st.invstd, st.e_mean, st.e_invstd = mean, invstd, e_mean, e_invstd
     return st
 
 
@@ -166,50 +103,6 @@ def _running_ref(st, rm0, rv0):
     e_rm = MOM * st.e_mean + 3 * U * (((1 - MOM) * rm0).abs() + (MOM * st.mean).abs())
     e_rv = MOM * unb * (st.e_var + U * st.var) + 3 * U * (((1 - MOM) * rv0).abs() + (MOM * st.var * unb).abs())
     return rm, e_rm, rv, e_rv
-
-
-def _bwd_ref(x, g, st, gamma, train, chain, e_g=None, e_sums=None):
-    """dbeta, dgamma, dx of BatchNorm in float64 from the masked gradient g, and their bounds.  st: the statistics the kernel
-    is GIVEN and their error against the true ones; chain: the reduce pass's; e_g: the error g itself arrives with;
-    e_sums: (e_dbeta, e_dgamma) of sums that were not formed by the reduce pass"""
-    xd = x.double()
-    rows = xd.shape[0]
-    xc = xd - st.mean
-    xh = xc * st.invstd
-    e_xh = st.invstd * st.e_mean + xc.abs() * st.e_invstd + 2 * U * xh.abs()
-    gx = g * xh
-    dbeta, dgamma = g.sum(0), gx.sum(0)
-    if e_sums is None:
-        e_db = chain * U * g.abs().sum(0) + U * dbeta.abs()
-        e_dg = (chain + 1) * U * gx.abs().sum(0) + (g.abs() * e_xh).sum(0) + U * dgamma.abs()
-        if e_g is not None:
-            e_db = e_db + e_g.sum(0)
-            e_dg = e_dg + (e_g * xh.abs()).sum(0)
-    else:
-        e_db, e_dg = e_sums
-    k0 = gamma * st.invstd
-    e_k0 = gamma.abs() * st.e_invstd + U * k0.abs()
-    zero = torch.zeros_like(dbeta)
-    k1, k2 = (dbeta / rows, dgamma / rows) if train else (zero, zero)
-    e_k1, e_k2 = (e_db / rows + U * k1.abs(), e_dg / rows + U * k2.abs()) if train else (zero, zero)
-    inner = g - k1 - xh * k2
-    dx = k0 * inner
-    e_dx = (k0.abs() * (e_k1 + xh.abs() * e_k2 + k2.abs() * e_xh + (0.0 if e_g is None else e_g)) + e_k0 * inner.abs() +
-            4 * U * k0.abs() * (g.abs() + k1.abs() + (xh * k2).abs()))
-    return dbeta, e_db, dgamma, e_dg, dx, e_dx
-
-
-def _params(gen, c, affine):
-    if not affine:
-        return None, None, torch.ones(c, dtype=torch.float64), torch.zeros(c, dtype=torch.float64)
-    gamma = (0.5 + torch.rand(c, generator=gen)) * torch.where(torch.rand(c, generator=gen) < 0.25, -1.0, 1.0)
-    beta = 0.5 * torch.randn(c, generator=gen)
-    return gamma, beta, gamma.double(), beta.double()
-
-
-def _data(gen, rows, c):
-    """seeded randn with a scale and an offset of its own per channel"""
-    return torch.randn(rows, c, generator=gen) * (0.5 + 1.5 * torch.rand(c, generator=gen)) + 2 * torch.rand(c, generator=gen) - 1
 
 
 def _mask_gradient(gen, pre, e_pre, relu, what):

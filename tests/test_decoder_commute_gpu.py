@@ -104,3 +104,87 @@ def test_bn_relu_classifier_pass_on_ragged_shapes(cuda, c, k, hw):
     names = ('out', 'dx', 'dconv', 'dgamma', 'dbeta', 'dcls_w', 'dcls_b', 'running_mean', 'running_var')
     for name, a, b in zip(names, res[0], res[1]):
         assert rel(a, b) < 5e-5, (name, rel(a, b))
+
+
+@pytest.mark.parametrize('bias,foreign', [(False, False), (True, True), (False, True)], ids=['no_bias', 'foreign_weight', 'both'])
+def test_bn_relu_classifier_pass_without_bias_and_with_a_weight_outside_ohwi_memory(cuda, bias, foreign):
+    """HF.bn_relu_dot with a classifier that has no bias, and with one whose weight lies [C][K] in memory (a 1x1 weight is OHWI
+    in both dense formats; a transposed one is in neither): weight.grad comes back with the parameter's strides, bias.grad
+    is absent without a bias, and the values are those of the three layers one by one."""
+    from ever_amd.hip import functional as HF
+    from ever_amd.module.layers import BatchNorm2d, Conv2d
+    c, k, hw = 64, 3, (9, 11)
+    torch.manual_seed(c + k)
+    conv = Conv2d(32, c, 3, 1, 1, bias=False).to(cuda)
+    bn = BatchNorm2d(c).to(cuda).train()
+    cls = Conv2d(c, k, 1, bias=bias).to(cuda)
+    if foreign:
+        cls.weight.data = cls.weight.data.reshape(k, c).t().contiguous().t().reshape(k, c, 1, 1)
+        assert cls.weight.stride()[:2] == (1, k) and not HF.is_nhwc(cls.weight)
+    strides = cls.weight.stride()
+    torch.nn.init.uniform_(bn.weight, 0.5, 1.5)
+    torch.nn.init.uniform_(bn.bias, -0.3, 0.3)
+    x = torch.randn(3, 32, *hw, device=cuda).contiguous(memory_format=torch.channels_last)
+    g = torch.randn(3, k, *hw, device=cuda)
+    res = []
+    for fused in (True, False):
+        for m in (conv, bn, cls):
+            m.zero_grad(set_to_none=True)
+        bn.reset_running_stats()
+        xi = x.clone().requires_grad_()
+        z = conv(xi, bn_stats=True)
+        out = HF.bn_relu_dot(z, bn, cls) if fused else cls(bn(z, relu=True))
+        assert out is not None, 'the fused form should take this shape'
+        (out * g).sum().backward()
+        torch.cuda.synchronize()
+        assert cls.weight.grad.stride() == strides, (fused, cls.weight.grad.stride(), strides)
+        assert cls.bias is None or cls.bias.grad is not None
+        res.append((out.detach(), xi.grad, conv.weight.grad.clone(), bn.weight.grad.clone(), bn.bias.grad.clone(),
+                    cls.weight.grad.clone()) + ((cls.bias.grad.clone(),) if bias else ()))
+
+    def rel(a, b):
+        return float((a.double() - b.double()).abs().max() / b.double().abs().max())
+    names = ('out', 'dx', 'dconv', 'dgamma', 'dbeta', 'dcls_w', 'dcls_b')
+    for name, a, b in zip(names, res[0], res[1]):
+        assert rel(a, b) < 5e-5, (name, rel(a, b))
+
+
+def test_bn_relu_classifier_pass_takes_what_its_plan_admits_and_nothing_else(cuda):
+    """HF.bn_relu_dot returns None and leaves the statistics records on z for a shape without an instantiation (C = 260 with
+    5 classes), a 3x3 classifier and 17 classes; it takes three register chunks rounded to four (C = 516, K = 3) and the
+    shape that sits exactly on the backward's LDS budget (C = 256, K = 12), forward and backward.  (The convolution kernels
+    leave records only for whole 64-channel tiles: z carries one record formed here, as an epilogue would have left it.)"""
+    from ever_amd.hip import functional as HF
+    from ever_amd.module.layers import BatchNorm2d, Conv2d
+    torch.manual_seed(11)
+    n, h, w = 2, 6, 10
+    for c, k, ks, takes in ((260, 5, 1, False), (64, 2, 3, False), (64, 17, 1, False), (516, 3, 1, True), (256, 12, 1, True)):
+        bn = BatchNorm2d(c).to(cuda).train()
+        cls = Conv2d(c, k, ks, 1, ks // 2).to(cuda)
+        assert HF.bn_relu_dot_admits(c, k, cls.weight.shape[2:]) == takes
+        z0 = (torch.randn(n, c, h, w, device=cuda) + 0.3).contiguous(memory_format=torch.channels_last)
+        rows = z0.permute(0, 2, 3, 1).reshape(-1, c).double()
+        record = torch.stack([torch.full((c,), float(n * h * w), dtype=torch.float64, device=cuda), rows.mean(0),
+                              ((rows - rows.mean(0)) ** 2).sum(0)]).float().contiguous()
+        z = z0.clone().requires_grad_()
+        parts = (record, 1, False)
+        z._evk_bn_parts = parts
+        out = HF.bn_relu_dot(z, bn, cls)
+        if not takes:
+            assert out is None and z._evk_bn_parts is parts, (c, k, ks)
+            continue
+        assert out is not None and out.shape == (n, k, h, w) and not hasattr(z, '_evk_bn_parts'), (c, k)
+        g = torch.randn(n, k, h, w, device=cuda)
+        (out * g).sum().backward()
+        torch.cuda.synchronize()
+        got = (out.detach(), z.grad, bn.weight.grad.clone(), bn.bias.grad.clone(), cls.weight.grad.clone(), cls.bias.grad.clone())
+        for m in (bn, cls):
+            m.zero_grad(set_to_none=True)
+        z1 = z0.clone().requires_grad_()
+        ref = cls(bn(z1, relu=True))
+        (ref * g).sum().backward()
+        torch.cuda.synchronize()
+        want = (ref.detach(), z1.grad, bn.weight.grad, bn.bias.grad, cls.weight.grad, cls.bias.grad)
+        for name, a, b in zip(('out', 'dz', 'dgamma', 'dbeta', 'dcls_w', 'dcls_b'), got, want):
+            err = float((a.double() - b.double()).abs().max() / b.double().abs().max())
+            assert err < 5e-5, (c, k, name, err)
