@@ -1,5 +1,5 @@
 """What the float64 tests of the BatchNorm family share (tests/test_bn_gpu.py: bn.hip, bn_pool.hip; tests/test_bn_dot_gpu.py:
-bn_dot.hip): NaN-filled outputs inside sentinel-guarded allocations, the error / bound assertion, the operand-scale check, the
+bn_dot.hip; tests/test_relation_bn_edges_gpu.py with tests/relation_ref_common.py: relation.hip's BatchNorm form): NaN-filled outputs inside sentinel-guarded allocations, the error / bound assertion, the operand-scale check, the
 float64 BatchNorm backward with its derived bounds (u = 2^-24; DESIGN.md §6b carries the derivation) and the seeded inputs."""
 import torch
 

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 # (N, C, HW), each for one reason
 CASES = [
     (1, 4, 1),          # one lane, one pixel, one block
-    (2, 260, 65),       # C / 4 = 65: lane 0 takes a second channel trip; two blocks per image, the second holds one pixel
+    (2, 260, 65),       # C / 4 = 65: lane 0 takes a second channel trip; two blocks per image of 33 and 32 pixels
     (3, 4, 16448),      # 256 blocks (the cap) of 65 pixels: the last two of every image own none and still store zero partials;
                         # 49344 pixels > the 32768 of one forward grid pass: a ragged second trip of the wave-stride loop
     (1, 4096, 3),       # the backward's limit C <= 4096: 64 KB of dynamic LDS
