@@ -216,6 +216,16 @@ def _take_handoff(y):
     return y
 
 
+def _take_parts(t):
+    """The BatchNorm statistics records riding on `t` (`_evk_bn_parts`, left by the convolution that produced it), taken
+    off it — one consumer uses them — or None.  (A consumer that may still decline looks with getattr first: the records
+    then stay for the layer-by-layer path.)"""
+    parts = getattr(t, '_evk_bn_parts', None)
+    if parts is not None:
+        del t._evk_bn_parts
+    return parts
+
+
 def _affine_grads(weight, c, dev):
     """(dgamma, dbeta) to write into, or (None, None) for a BatchNorm without affine parameters"""
     if weight is None:

@@ -66,13 +66,21 @@ def _conv_desc(n, h, w, cin, cout, kh, kw, stride, padding, dilation):
     sh, sw = stride
     ph, pw = padding
     dh, dw = dilation
-    ho = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (w + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    return _C.ConvDesc(n, h, w, cin, ho, wo, cout, kh, kw, sh, sw, ph, pw, dh, dw)
+    return _C.ConvDesc(n, h, w, cin, _conv_out(h, kh, sh, ph, dh), _conv_out(w, kw, sw, pw, dw), cout, kh, kw, sh, sw, ph, pw,
+                       dh, dw)
 
 
 def _pad4(c):
     return (c + 3) // 4 * 4
+
+
+def conv_channel_padding(cin, cout, planes):
+    """(cin_p, cout_p, narrow8): Cin and Cout as the kernels see them, padded to multiples of 4; narrow heads (classifier
+    Cout = 1..7) pad dy / weight rows to 8 output channels under the plane arithmetics (`planes`), so that the data gradient
+    stays on the split-MFMA kernels (its reduction is over taps x Cout).  The forward writes the unpadded Cout."""
+    cin_p = _pad4(cin)
+    narrow8 = bool(planes and cin_p == cin and cout % 8 != 0 and cout < 8 and os.environ.get('EVK_NARROW_X3', '1') != '0')
+    return cin_p, (8 if narrow8 else _pad4(cout)), narrow8
 
 
 def _pad_last(t2d_ptr, rows, c, cp, device):
@@ -126,6 +134,30 @@ def _drop(states):
         cs.xk = cs.y = cs.weight = cs.w_ohwi = cs.bias_leaf = None
 
 
+def _stats_request(d, dev):
+    """(records tensor, capacity) for a forward launch that is to leave BatchNorm partial statistics of its output"""
+    cap = int(_C.load().evk_conv2d_stats_max_parts(ctypes.byref(d)))
+    return torch.empty((cap * 3 * d.Cout,), device=dev, dtype=torch.float32), cap
+
+
+def _launch_forward(d, x_ptr, xbits, pl_ptr, wabs_ptr, bias, y, flags, st, parts=None, cap=0, ybits=None, x_pk=False):
+    """The forward launch of the current plane arithmetic (f16x2 where wabs_ptr is given) -> number of statistics records
+    written into parts / cap (a `_stats_request`).  ybits, x_pk (packed x): f16x2 only.  See DESIGN §3."""
+    nparts = ctypes.c_int32(0)
+    if wabs_ptr is not None:
+        _C.call('evk_conv2d_fwd_f16x2', ctypes.byref(d), x_ptr, xbits.data_ptr(), pl_ptr, wabs_ptr, _ptr(bias), None,
+                y.data_ptr(), flags | (2 if x_pk else 0), _ptr(parts), cap, ctypes.byref(nparts), _ptr(ybits), st)
+    elif get_conv_math() == 'bf16':
+        _C.call('evk_conv2d_fwd_bf16', ctypes.byref(d), x_ptr, pl_ptr, _ptr(bias), y.data_ptr(), flags, _ptr(parts), cap,
+                ctypes.byref(nparts), st)
+    elif parts is not None:
+        _C.call('evk_conv2d_fwd_x3_stats', ctypes.byref(d), x_ptr, pl_ptr, _ptr(bias), y.data_ptr(), flags, parts.data_ptr(), cap,
+                ctypes.byref(nparts), st)
+    else:
+        _C.call('evk_conv2d_fwd_x3', ctypes.byref(d), x_ptr, pl_ptr, _ptr(bias), y.data_ptr(), flags, st)
+    return int(nparts.value)
+
+
 def _conv_forward(x, weight, bias, stride, padding, dilation, relu, want_stats=False):
     """evk_conv2d_fwd on NHWC x / OHWI weight -> (y, _ConvState).  want_stats: also the BatchNorm partial statistics of
     y from the epilogue (cs.bn_parts = (records tensor, count) or None when this shape's kernel cannot)."""
@@ -133,17 +165,14 @@ def _conv_forward(x, weight, bias, stride, padding, dilation, relu, want_stats=F
     cout, cin_w, kh, kw = weight.shape
     if cin_w != cin:
         raise ValueError(f'conv2d: input has {cin} channels but weight expects {cin_w} (groups != 1 unsupported)')
-    dev = x.device
-    st = _stream()
+    dev, st = x.device, _stream()
     w_ohwi = _weight_ohwi(weight.detach())
     cin_p = _pad4(cin)
+    xk, wk = x, w_ohwi
     if cin_p != cin:
         xk = _pad_last(x.data_ptr(), n * h * w, cin, cin_p, dev)
         wk = _pad_last(w_ohwi.data_ptr(), cout * kh * kw, cin, cin_p, dev)
-        x_ptr, w_ptr = xk.data_ptr(), wk.data_ptr()
-    else:
-        xk = x
-        x_ptr, w_ptr = x.data_ptr(), w_ohwi.data_ptr()
+    x_ptr, w_ptr = xk.data_ptr(), wk.data_ptr()
     d = _conv_desc(n, h, w, cin_p, cout, kh, kw, stride, padding, dilation)
     x_pk = _is_packed(x)        # written packed by the BatchNorm pass before this convolution (EVK_BN_PACK_Y)
     if x_pk and not (_f16x2() and cin_p == cin and cin % 8 == 0 and n * d.Ho * d.Wo > 32):
@@ -167,45 +196,27 @@ def _conv_forward(x, weight, bias, stride, padding, dilation, relu, want_stats=F
         xbits = absmax_bits(x, st) if wabs_ptr is not None else None
         sp = timing.span('conv_igemm', cs.flops, cs.abytes)
         stats = want_stats and _BN_EPILOGUE and not relu and cout % 4 == 0
-        parts, cap, nparts = None, 0, ctypes.c_int32(0)
-        if stats:
-            cap = int(_C.load().evk_conv2d_stats_max_parts(ctypes.byref(d)))
-            parts = torch.empty((cap * 3 * cout,), device=dev, dtype=torch.float32)
-        if wabs_ptr is not None:
-            # an output that no BatchNorm will normalise is (mostly) another convolution's operand: its scale from here
-            ybits = None if stats else _amax_zeroed(dev)
-            _C.call('evk_conv2d_fwd_f16x2', ctypes.byref(d), x_ptr, xbits.data_ptr(), pl_ptr, wabs_ptr, _ptr(bias), None,
-                    y.data_ptr(), (1 if relu else 0) | (2 if x_pk else 0), _ptr(parts), cap, ctypes.byref(nparts),
-                    _ptr(ybits), st)
-            if ybits is not None:
-                _note_amax(y, ybits)
-        elif get_conv_math() == 'bf16':
-            _C.call('evk_conv2d_fwd_bf16', ctypes.byref(d), x_ptr, pl_ptr, _ptr(bias), y.data_ptr(), 1 if relu else 0,
-                    _ptr(parts), cap, ctypes.byref(nparts), st)
-        elif stats:
-            _C.call('evk_conv2d_fwd_x3_stats', ctypes.byref(d), x_ptr, pl_ptr, _ptr(bias), y.data_ptr(), 0,
-                    parts.data_ptr(), cap, ctypes.byref(nparts), st)
-        else:
-            _C.call('evk_conv2d_fwd_x3', ctypes.byref(d), x_ptr, pl_ptr, _ptr(bias), y.data_ptr(),
-                    1 if relu else 0, st)
-        if nparts.value > 0:
+        parts, cap = _stats_request(d, dev) if stats else (None, 0)
+        # an output that no BatchNorm will normalise is (mostly) another convolution's operand: its scale from here
+        ybits = _amax_zeroed(dev) if (wabs_ptr is not None and not stats) else None
+        nparts = _launch_forward(d, x_ptr, xbits, pl_ptr, wabs_ptr, bias, y, 1 if relu else 0, st, parts, cap, ybits, x_pk)
+        if ybits is not None:
+            _note_amax(y, ybits)
+        if nparts > 0:
             # third field: this convolution's backward takes its dy packed (the BatchNorm that consumes the records is
             # the ONLY reader of y — conv2d(bn_stats=True)'s contract — so its dx has no other reader either)
             # (the planar weight gradient packs both operands itself: its BatchNorm's dx stays fp32)
-            bn_parts = (parts, int(nparts.value),
-                        _PACKED and wabs_ptr is not None and bias is None and cout % 8 == 0 and not observers_active()
-                        and not _wgrad_planar_pays(d))
+            bn_parts = (parts, nparts, _PACKED and wabs_ptr is not None and bias is None and cout % 8 == 0
+                        and not observers_active() and not _wgrad_planar_pays(d))
     else:
         sp = timing.span('conv_igemm_f32', cs.flops, cs.abytes)
         _C.call('evk_conv2d_fwd', ctypes.byref(d), x_ptr, w_ptr, _ptr(bias), y.data_ptr(), 1 if relu else 0, st)
-    if sp is not None:
-        sp.stop()
-    cs.desc, cs.relu, cs.cin, cs.has_bias = d, relu, cin, bias is not None
+    timing.stop(sp)
+    cs.desc, cs.relu, cs.cin, cs.has_bias, cs.bn_parts = d, relu, cin, bias is not None, bn_parts
     cs.bias_leaf = bias      # (the parameter itself, not saved for backward: the weight-gradient side stream's rules look at it)
     cs.w_stride = tuple(weight.stride())
     # xk (channel-padded copy when Cin % 4 != 0) is what wgrad reads
     cs.xk, cs.w_ohwi, cs.y, cs.weight = xk, w_ohwi, (y if relu else None), weight
-    cs.bn_parts = bn_parts
     return y, cs
 
 
@@ -219,15 +230,12 @@ def _sparse_dgrad(cs):
 
 def _conv_backward(cs, dy, need_dx, need_dw, need_db, accum=None, inplace=False, accum_bits=None):
     """(dx, dw, db) of one convolution.  `accum` (a tensor of x's shape or None) is added to dx inside
-    the data-gradient epilogue: dx = conv_transpose(dy, w) + accum; with `inplace` (plane kernels only) dx IS accum."""
-    d, xk, w_ohwi = cs.desc, cs.xk, cs.w_ohwi
-    dev = dy.device
-    st = _stream()
-    n, cin_p, cout, kh, kw = d.N, d.Cin, d.Cout, d.kh, d.kw
-    cin = cs.cin
+    the data-gradient epilogue: dx = conv_transpose(dy, w) + accum; with `inplace` (plane kernels only) dx IS accum.
+    dy as the kernels read it, once; then `_dgrad_planes` or `_dgrad_f32` and `_wgrad` in the early-fork rule's order."""
+    d, dev, st, cin, cout = cs.desc, dy.device, _stream(), cs.cin, cs.desc.Cout
     dy = materialize_lazy(dy)       # (an unmasked gradient with ReLU bits is only understood as `accum`)
     if accum_bits is not None and not (need_dx and _f16x2() and d.stride_h == 1 and d.stride_w == 1 and not inplace
-                                       and cin_p == cin and cin % 8 == 0 and cout % 8 == 0):
+                                       and d.Cin == cin and cin % 8 == 0 and cout % 8 == 0):
         accum, accum_bits = materialize_lazy(accum), None
     dy = as_nhwc(dy, 'conv2d.backward')
     dy_pk = _is_packed(dy)      # written packed by the BatchNorm backward that follows this convolution
@@ -237,186 +245,11 @@ def _conv_backward(cs, dy, need_dx, need_dw, need_db, accum=None, inplace=False,
         g = torch.empty_like(dy)
         _C.call('evk_relu_bwd', dy.data_ptr(), cs.y.data_ptr(), g.data_ptr(), dy.numel(), st)
         dy = g
-    rows_o = n * d.Ho * d.Wo
     x3 = _planes_math()
-    # narrow heads (classifier Cout = 1..7): pad dy / weight rows — to 8 output channels under the split arithmetic, so
-    # that the data gradient stays on the split-MFMA kernels (its reduction is over taps x Cout), else to 4
-    narrow8 = x3 and cin_p == cin and cout % 8 != 0 and cout < 8 and os.environ.get('EVK_NARROW_X3', '1') != '0'
-    cout_p = 8 if narrow8 else _pad4(cout)
-    if cout_p != cout:
-        dyk = _pad_last(dy.data_ptr(), rows_o, cout, cout_p, dev)
-        dy_ptr = dyk.data_ptr()
-    else:
-        dyk = dy
-        dy_ptr = dy.data_ptr()
-    dk = _C.ConvDesc(d.N, d.H, d.W, cin_p, d.Ho, d.Wo, cout_p, kh, kw, d.stride_h, d.stride_w, d.pad_h, d.pad_w,
+    cin_p, cout_p, narrow8 = conv_channel_padding(cin, cout, x3)      # (cin_p is the forward's: d.Cin)
+    dyk = _pad_last(dy.data_ptr(), d.N * d.Ho * d.Wo, cout, cout_p, dev) if cout_p != cout else dy
+    dk = _C.ConvDesc(d.N, d.H, d.W, cin_p, d.Ho, d.Wo, cout_p, d.kh, d.kw, d.stride_h, d.stride_w, d.pad_h, d.pad_w,
                      d.dil_h, d.dil_w)
-    dx = dw = db = None
-    taps = kh * kw
-
-    def _dgrad():
-        nonlocal dx, accum, accum_bits
-        if need_dx and x3 and cin_p == cin and (narrow8 or (cout_p == cout and cout % 8 == 0)):
-            if narrow8:     # zero rows appended to the (tiny) weight: a transient copy, split on every call
-                w_src = torch.zeros((cout_p, taps, cin), device=dev, dtype=torch.float32)
-                w_src[:cout].copy_(w_ohwi.permute(0, 2, 3, 1).reshape(cout, taps, cin))
-            else:
-                w_src = w_ohwi
-            pl_ptr, wabs_ptr, _keep = _weight_planes(cs.weight, w_src, w_src.data_ptr(), dk, 1, st, dev)
-            acc_ptr = None
-            if accum is not None:
-                accum = as_nhwc(accum, 'conv2d.backward.accum')
-                acc_ptr = accum.data_ptr()
-            dx = accum if (inplace and accum is not None) else empty_nhwc(n, cin, d.H, d.W, dev)
-            dybits = absmax_bits(dyk, st) if wabs_ptr is not None else None
-            sp = timing.span('conv_igemm', cs.flops, cs.abytes, cs.scope)
-            if wabs_ptr is not None:
-                # in place: the slots the main branch's launch raised stay (an upper bound is all a scale needs)
-                hit = getattr(dx, '_evk_amax', None) if inplace else None
-                dxbits = hit[2] if hit is not None else _amax_zeroed(dev)
-                if accum_bits is not None and acc_ptr is not None:
-                    relu_bits_stats['masked_dgrad'] += 1
-                    _C.call('evk_conv2d_dgrad_f16x2_masked', ctypes.byref(dk), dy_ptr, dybits.data_ptr(), pl_ptr, wabs_ptr,
-                            acc_ptr, accum_bits.data_ptr(), dx.data_ptr(), _ptr(dxbits), 4 if dy_pk else 0, st)
-                else:
-                    _C.call('evk_conv2d_dgrad_f16x2_ex', ctypes.byref(dk), dy_ptr, dybits.data_ptr(), pl_ptr, wabs_ptr, acc_ptr,
-                            dx.data_ptr(), _ptr(dxbits), 4 if dy_pk else 0, st)
-                if dxbits is not None:
-                    _note_amax(dx, dxbits)
-            else:
-                _C.call(_entry('evk_conv2d_dgrad_x3'), ctypes.byref(dk), dy_ptr, pl_ptr, acc_ptr, dx.data_ptr(), st)
-            if sp is not None:
-                sp.stop()
-        elif need_dx:
-            # weights as [cout_p][taps][cin_p]
-            if cin_p != cin or cout_p != cout:
-                wfull = torch.zeros((cout_p, taps, cin_p), device=dev, dtype=torch.float32)
-                tmp = (_pad_last(w_ohwi.data_ptr(), cout * taps, cin, cin_p, dev) if cin_p != cin
-                       else w_ohwi.permute(0, 2, 3, 1))  # OHWI memory order
-                wfull[:cout].copy_(tmp.reshape(cout, taps, cin_p))
-                w_src = wfull
-            else:
-                w_src = w_ohwi
-            wt = torch.empty((cin_p, taps, cout_p), device=dev, dtype=torch.float32)
-            _C.call('evk_conv2d_pack_dgrad_weight', ctypes.byref(dk), w_src.data_ptr(), wt.data_ptr(), st)
-            acc_ptr = None
-            if accum is not None:
-                if cin_p != cin:
-                    raise HipPathError('conv2d.backward: accum with channel-padded inputs is not supported')
-                accum = as_nhwc(accum, 'conv2d.backward.accum')
-                acc_ptr = accum.data_ptr()
-            dxk = empty_nhwc(n, cin_p, d.H, d.W, dev)
-            sp = timing.span('conv_igemm_f32', cs.flops, cs.abytes, cs.scope)
-            _C.call('evk_conv2d_dgrad', ctypes.byref(dk), dy_ptr, wt.data_ptr(), acc_ptr, dxk.data_ptr(), st)
-            if sp is not None:
-                sp.stop()
-            if cin_p != cin:
-                dx = empty_nhwc(n, cin, d.H, d.W, dev)
-                _C.call('evk_unpad_channels', dxk.data_ptr(), dx.data_ptr(), n * d.H * d.W, cin_p, cin, st)
-            else:
-                dx = dxk
-
-    def _wgrad():
-        nonlocal dw, db
-        if need_dw or need_db:
-            lib = _C.load()
-            ws_bytes = (lib.evk_conv2d_wgrad_x3_workspace_bytes if x3 else lib.evk_conv2d_wgrad_workspace_bytes)(
-                ctypes.byref(dk))
-            dwk = torch.empty((cout_p, taps, cin_p), device=dev, dtype=torch.float32)
-            dbk = torch.empty((cout_p,), device=dev, dtype=torch.float32) if need_db else None
-            # (the gradient comes in OHWI memory order: a parameter laid out otherwise gets a deep copy from AccumulateGrad —
-            # a read of dw on the backward's stream — so its weight gradient stays there)
-            wstr = cs.w_stride
-            contract = tuple(wstr) == (taps * cin, 1, kw * cin, cin) or (taps == 1 and wstr[0] == cin and wstr[1] == 1)
-            side = _wgrad_side_stream(dev, cs.weight, cs.bias_leaf if need_db else None) if contract else None
-
-            # with BATCHED side-stream launches (graph capture: EVK_WGRAD_BATCH = 32) the closure would look at host-side
-            # tensor state — the operand-scale caches, the packed flag — up to 32 layers after this layer's backward ran; what it
-            # needs is resolved here, when the launch is queued.  (A batch of one runs the closure right away: nothing to resolve,
-            # and a missing scale is then computed on the side stream, off the backward's chain.)
-            pre = None
-            if side is not None and _WGRAD_BATCH[0] > 1 and x3 and _f16x2():
-                pre = (absmax_bits(xk, st), absmax_bits(dyk, st), _is_packed(xk))
-
-            # the half-chip split-K plan is a property of the CONFIGURATION (side stream enabled + split on), not of the stream
-            # this launch ends up on (the probe that picks the side stream is a timing measurement, and a launch that
-            # fell back to the backward's stream used to take the other plan — other bits for the same model and switches)
-            shared = _WGRAD_SHARED if (_WGRAD_STREAM[0] and _WGRAD_SHARED_ON[0]) else 0
-
-            def launch(st):
-                """the weight-gradient launches of this layer on stream `st` (torch's current stream when this runs)"""
-                ws = workspace(dev, ws_bytes)
-                h2 = x3 and _f16x2()
-                dy_pk_ = dy_pk
-                sp = timing.span('conv_wgrad' if x3 else 'conv_wgrad_f32', cs.flops, cs.abytes, cs.scope)
-                if h2:
-                    if pre is not None:
-                        xbits, dybits, x_pk = pre
-                    else:
-                        xbits, dybits, x_pk = absmax_bits(xk, st), absmax_bits(dyk, st), _is_packed(xk)
-                    if side is not None:     # (slices of a pooled buffer of the main stream: keep the pool block until this has run)
-                        _wgrad_hold(xbits, dybits)
-                    xw_ptr, dyw_ptr, _tmp = xk.data_ptr(), dy_ptr, None
-                    planar = 0
-                    if cout_p == cout and cin_p == cin and not x_pk and not dy_pk_ and _wgrad_planar_pays(dk, need_db):
-                        xq, dq = torch.empty_like(xk), torch.empty_like(dyk)
-                        _C.call('evk_pack_planar_f16x2', xk.data_ptr(), xk.numel(), xbits.data_ptr(), xq.data_ptr(), st)
-                        _C.call('evk_pack_planar_f16x2', dy_ptr, dyk.numel(), dybits.data_ptr(), dq.data_ptr(), st)
-                        xw_ptr, dyw_ptr, _tmp, planar = xq.data_ptr(), dq.data_ptr(), [xq, dq], 8 | 16
-                    elif _PACKED and not need_db and cout_p == cout and _wgrad_pack_pays(cs.flops, 0 if x_pk else xk.numel(),
-                                                                                     0 if dy_pk_ else dyk.numel()):
-                        # the kernel's bound is the split of its operands while staging (each element is staged by many
-                        # workgroups): where the matrix work per byte is high, one streaming pass that stores them split first
-                        _tmp = []
-                        if not x_pk:
-                            xp = torch.empty_like(xk)
-                            _C.call('evk_pack_f16x2', xk.data_ptr(), xk.numel(), xbits.data_ptr(), xp.data_ptr(), st)
-                            xw_ptr, x_pk = xp.data_ptr(), True
-                            _tmp.append(xp)
-                        if not dy_pk_:
-                            dp = torch.empty_like(dyk)
-                            _C.call('evk_pack_f16x2', dy_ptr, dyk.numel(), dybits.data_ptr(), dp.data_ptr(), st)
-                            dyw_ptr, dy_pk_ = dp.data_ptr(), True
-                            _tmp.append(dp)
-                    _C.call('evk_conv2d_wgrad_f16x2_ex', ctypes.byref(dk), xw_ptr, xbits.data_ptr(), dyw_ptr, dybits.data_ptr(),
-                            dwk.data_ptr(), _ptr(dbk), ws.data_ptr(), ws_bytes,
-                            (planar if planar else ((2 if x_pk else 0) | (4 if dy_pk_ else 0))) | shared, st)
-                else:
-                    _C.call(_entry('evk_conv2d_wgrad_x3') if x3 else 'evk_conv2d_wgrad', ctypes.byref(dk), xk.data_ptr(), dy_ptr,
-                            dwk.data_ptr(), _ptr(dbk), ws.data_ptr(), ws_bytes, st)
-                if sp is not None:
-                    sp.stop()
-                if dw2 is not None:
-                    _C.call('evk_unpad_channels', dwk.data_ptr(), dw2.data_ptr(), cout_p * taps, cin_p, cin, st)
-
-            # the tensors autograd gets are fixed now; the launches that fill them may come later (side stream, in batches)
-            dw2 = torch.empty((cout_p * taps, cin), device=dev, dtype=torch.float32) if (need_dw and cin_p != cin) else None
-            if need_dw:
-                dwv = dw2.reshape(cout_p, taps, cin) if dw2 is not None else dwk
-                # logical OIHW view over OHWI memory (matches a channels_last parameter)
-                dw = dwv[:cout].reshape(cout, kh, kw, cin).permute(0, 3, 1, 2)
-                wstr = cs.w_stride
-                if kh * kw == 1 and dw.stride() != wstr and wstr[0] == cin and wstr[1] == 1:
-                    # 1x1 kernels: the size-1 dims make the stride tuple ambiguous; present exactly the
-                    # parameter's strides so AccumulateGrad / DDP bucket views alias instead of copying
-                    dw = dw.as_strided(dw.shape, wstr)
-            if need_db:
-                db = dbk[:cout]
-            if side is None:
-                launch(st)
-            else:
-                # the weight gradient beside the rest of the backward (see _WGRAD_STREAM above).  Its launches are QUEUED and
-                # issued in batches: one fork event, one switch of torch's current stream and back per batch instead of per
-                # layer (host time), and a captured step has a handful of edges between its two branches instead of 2 x 53
-                _wgrad_hold(xk, dyk, dwk, dbk, dw2)
-                _WGRAD_QUEUE.setdefault(dev, []).append(launch)
-                if need_dw:              # what AccumulateGrad has to store as it is (checked at the end of the pass)
-                    _WGRAD_OWNED[id(cs.weight)] = (cs.weight, dw.untyped_storage().data_ptr())
-                if need_db:
-                    _WGRAD_OWNED[id(cs.bias_leaf)] = (cs.bias_leaf, db.untyped_storage().data_ptr())
-                if len(_WGRAD_QUEUE.get(dev, ())) >= _WGRAD_BATCH[0]:
-                    flush_wgrad_queue(dev)
-
     # EVK_WGRAD_EARLY=1 (A/B): the weight gradient is forked BEFORE the data gradient is enqueued, so that it may start
     # beside it instead of behind it; the operand scale of dy is fixed first (both read it, from different streams)
     # EVK_WGRAD_EARLY=2 (round 5): only the layers whose weight gradient is the nine-tap planar kernel (3x3x256 on the 128^2
@@ -426,14 +259,191 @@ def _conv_backward(cs, dy, need_dx, need_dw, need_db, accum=None, inplace=False,
     # with its own layer's 780 us halo data gradient — two long matrix-bound kernels, where nothing short waits.
     early = _WGRAD_EARLY_MODE == 1 or (_WGRAD_EARLY_MODE == 2 and need_dw and cout_p == cout and cin_p == cin and not dy_pk
                                        and _wgrad_planar_pays(dk, need_db))
-    if early and need_dx and (need_dw or need_db) and _f16x2() and x3:
+    wgrad_first = early and need_dx and (need_dw or need_db) and _f16x2() and x3
+    dx = dw = db = None
+    if wgrad_first:
         absmax_bits(dyk, st)
-        _wgrad()
-        _dgrad()
-    else:
-        _dgrad()
-        _wgrad()
+        dw, db = _wgrad(cs, dk, dyk, dy_pk, need_dw, need_db, x3, st)
+    if need_dx and x3 and cin_p == cin and (narrow8 or (cout_p == cout and cout % 8 == 0)):
+        dx = _dgrad_planes(cs, dk, dyk, dy_pk, narrow8, accum, accum_bits, inplace, st)
+    elif need_dx:
+        dx = _dgrad_f32(cs, dk, dyk, accum, st)
+    if (need_dw or need_db) and not wgrad_first:
+        dw, db = _wgrad(cs, dk, dyk, dy_pk, need_dw, need_db, x3, st)
     return dx, dw, db
+
+
+def _dgrad_planes(cs, dk, dyk, dy_pk, narrow8, accum, accum_bits, inplace, st):
+    """dx on the split-MFMA kernels of the current plane arithmetic (unpadded Cin; Cout a multiple of 8, or padded to 8)"""
+    d, w_ohwi, cin, dev = cs.desc, cs.w_ohwi, cs.cin, dyk.device
+    w_src = w_ohwi
+    if narrow8:     # zero rows appended to the (tiny) weight: a transient copy, split on every call
+        taps = d.kh * d.kw
+        w_src = torch.zeros((dk.Cout, taps, cin), device=dev, dtype=torch.float32)
+        w_src[:d.Cout].copy_(w_ohwi.permute(0, 2, 3, 1).reshape(d.Cout, taps, cin))
+    pl_ptr, wabs_ptr, _keep = _weight_planes(cs.weight, w_src, w_src.data_ptr(), dk, 1, st, dev)
+    if accum is not None:
+        accum = as_nhwc(accum, 'conv2d.backward.accum')
+    acc_ptr = _ptr(accum)
+    dx = accum if (inplace and accum is not None) else empty_nhwc(d.N, cin, d.H, d.W, dev)
+    dybits = absmax_bits(dyk, st) if wabs_ptr is not None else None
+    sp = timing.span('conv_igemm', cs.flops, cs.abytes, cs.scope)
+    if wabs_ptr is not None:
+        # in place: the slots the main branch's launch raised stay (an upper bound is all a scale needs)
+        hit = getattr(dx, '_evk_amax', None) if inplace else None
+        dxbits = hit[2] if hit is not None else _amax_zeroed(dev)
+        if accum_bits is not None and acc_ptr is not None:
+            relu_bits_stats['masked_dgrad'] += 1
+            _C.call('evk_conv2d_dgrad_f16x2_masked', ctypes.byref(dk), dyk.data_ptr(), dybits.data_ptr(), pl_ptr, wabs_ptr,
+                    acc_ptr, accum_bits.data_ptr(), dx.data_ptr(), _ptr(dxbits), 4 if dy_pk else 0, st)
+        else:
+            _C.call('evk_conv2d_dgrad_f16x2_ex', ctypes.byref(dk), dyk.data_ptr(), dybits.data_ptr(), pl_ptr, wabs_ptr, acc_ptr,
+                    dx.data_ptr(), _ptr(dxbits), 4 if dy_pk else 0, st)
+        if dxbits is not None:
+            _note_amax(dx, dxbits)
+    else:
+        _C.call(_entry('evk_conv2d_dgrad_x3'), ctypes.byref(dk), dyk.data_ptr(), pl_ptr, acc_ptr, dx.data_ptr(), st)
+    timing.stop(sp)
+    return dx
+
+
+def _dgrad_f32(cs, dk, dyk, accum, st):
+    """dx on the fp32 kernel, from the weight re-laid as [cin_p][taps][cout_p] (zero-filled where a channel count is padded)"""
+    d, w_ohwi, cin, cout = cs.desc, cs.w_ohwi, cs.cin, cs.desc.Cout
+    cin_p, cout_p, taps, dev = dk.Cin, dk.Cout, d.kh * d.kw, w_ohwi.device
+    w_src = w_ohwi      # weights as [cout_p][taps][cin_p]
+    if cin_p != cin or cout_p != cout:
+        w_src = torch.zeros((cout_p, taps, cin_p), device=dev, dtype=torch.float32)
+        tmp = (_pad_last(w_ohwi.data_ptr(), cout * taps, cin, cin_p, dev) if cin_p != cin
+               else w_ohwi.permute(0, 2, 3, 1))  # OHWI memory order
+        w_src[:cout].copy_(tmp.reshape(cout, taps, cin_p))
+    wt = torch.empty((cin_p, taps, cout_p), device=dev, dtype=torch.float32)
+    _C.call('evk_conv2d_pack_dgrad_weight', ctypes.byref(dk), w_src.data_ptr(), wt.data_ptr(), st)
+    if accum is not None:
+        if cin_p != cin:
+            raise HipPathError('conv2d.backward: accum with channel-padded inputs is not supported')
+        accum = as_nhwc(accum, 'conv2d.backward.accum')
+    dxk = empty_nhwc(d.N, cin_p, d.H, d.W, dev)
+    sp = timing.span('conv_igemm_f32', cs.flops, cs.abytes, cs.scope)
+    _C.call('evk_conv2d_dgrad', ctypes.byref(dk), dyk.data_ptr(), wt.data_ptr(), _ptr(accum), dxk.data_ptr(), st)
+    timing.stop(sp)
+    if cin_p == cin:
+        return dxk
+    dx = empty_nhwc(d.N, cin, d.H, d.W, dev)
+    _C.call('evk_unpad_channels', dxk.data_ptr(), dx.data_ptr(), d.N * d.H * d.W, cin_p, cin, st)
+    return dx
+
+
+def _as_param_strides(dw, w_stride, admits):
+    """1x1 kernels: the size-1 dims make the stride tuple ambiguous; present exactly the parameter's strides so that
+    AccumulateGrad / DDP bucket views alias instead of copying.  `admits`: the caller's test of w_stride."""
+    if dw.shape[2] * dw.shape[3] == 1 and dw.stride() != w_stride and admits:
+        return dw.as_strided(dw.shape, w_stride)
+    return dw
+
+
+def _launch_wgrad(d, x_ptr, dy_ptr, dw, db, ws, ws_bytes, st, x3=True, scales=None, flags=None):
+    """The weight-gradient launch: f16x2 where scales = (x, dy scale buffers) are given — the layer path's entry with its
+    `flags` word, the stem's without — else the plane kernel (x3) or the fp32 one.  See DESIGN §3."""
+    if scales is not None and flags is not None:
+        _C.call('evk_conv2d_wgrad_f16x2_ex', ctypes.byref(d), x_ptr, scales[0].data_ptr(), dy_ptr, scales[1].data_ptr(),
+                dw.data_ptr(), _ptr(db), ws.data_ptr(), ws_bytes, flags, st)
+    elif scales is not None:
+        _C.call('evk_conv2d_wgrad_f16x2', ctypes.byref(d), x_ptr, scales[0].data_ptr(), dy_ptr, scales[1].data_ptr(),
+                dw.data_ptr(), _ptr(db), ws.data_ptr(), ws_bytes, st)
+    else:
+        _C.call(_entry('evk_conv2d_wgrad_x3') if x3 else 'evk_conv2d_wgrad', ctypes.byref(d), x_ptr, dy_ptr, dw.data_ptr(),
+                _ptr(db), ws.data_ptr(), ws_bytes, st)
+
+
+def _wgrad_f16x2_operands(cs, dk, xk, dyk, xbits, dybits, x_pk, dy_pk, need_db, st):
+    """(x pointer, dy pointer, flag word, keep-alive) of a layer's f16x2 weight gradient: the operands as they are, or behind
+    a stand-alone pack pass where one pays: planar (both, nine-tap kernel) or plain (whichever is still fp32)"""
+    same_cout = dk.Cout == cs.desc.Cout
+    if same_cout and dk.Cin == cs.cin and not x_pk and not dy_pk and _wgrad_planar_pays(dk, need_db):
+        xw, dyw = _pack_pass('evk_pack_planar_f16x2', xk, xbits, st), _pack_pass('evk_pack_planar_f16x2', dyk, dybits, st)
+        return xw.data_ptr(), dyw.data_ptr(), 8 | 16, (xw, dyw)
+    xw, dyw = xk, dyk
+    if _PACKED and not need_db and same_cout and _wgrad_pack_pays(cs.flops, 0 if x_pk else xk.numel(),
+                                                                  0 if dy_pk else dyk.numel()):
+        # the kernel's bound is the split of its operands while staging (each element is staged by many
+        # workgroups): where the matrix work per byte is high, one streaming pass that stores them split first
+        if not x_pk:
+            xw, x_pk = _pack_pass('evk_pack_f16x2', xk, xbits, st), True
+        if not dy_pk:
+            dyw, dy_pk = _pack_pass('evk_pack_f16x2', dyk, dybits, st), True
+    return xw.data_ptr(), dyw.data_ptr(), (2 if x_pk else 0) | (4 if dy_pk else 0), (xw, dyw)
+
+
+def _pack_pass(entry, t, bits, st):
+    out = torch.empty_like(t)
+    _C.call(entry, t.data_ptr(), t.numel(), bits.data_ptr(), out.data_ptr(), st)
+    return out
+
+
+def _wgrad(cs, dk, dyk, dy_pk, need_dw, need_db, x3, st):
+    """(dw, db) of one layer: the tensors autograd gets are fixed here; the launches that fill them (`launch`) run now on the
+    backward's stream, or later on the side stream (hip/streams.py), in batches."""
+    d, xk, dev = cs.desc, cs.xk, dyk.device
+    cin, cout, cin_p, cout_p, kh, kw, taps = cs.cin, d.Cout, dk.Cin, dk.Cout, d.kh, d.kw, d.kh * d.kw
+    lib = _C.load()
+    ws_bytes = (lib.evk_conv2d_wgrad_x3_workspace_bytes if x3 else lib.evk_conv2d_wgrad_workspace_bytes)(ctypes.byref(dk))
+    dwk = torch.empty((cout_p, taps, cin_p), device=dev, dtype=torch.float32)
+    dbk = torch.empty((cout_p,), device=dev, dtype=torch.float32) if need_db else None
+    # (the gradient comes in OHWI memory order: a parameter laid out otherwise gets a deep copy from AccumulateGrad —
+    # a read of dw on the backward's stream — so its weight gradient stays there)
+    wstr = cs.w_stride
+    contract = tuple(wstr) == (taps * cin, 1, kw * cin, cin) or (taps == 1 and wstr[0] == cin and wstr[1] == 1)
+    side = _wgrad_side_stream(dev, cs.weight, cs.bias_leaf if need_db else None) if contract else None
+    h2 = x3 and _f16x2()
+    # ADVICE r4: with BATCHED side-stream launches (graph capture: EVK_WGRAD_BATCH = 32) the closure would look at host-side
+    # tensor state — the operand-scale caches, the packed flag — up to 32 layers after this layer's backward ran; what it
+    # needs is resolved here, when the launch is queued.  (A batch of one runs the closure right away: nothing to resolve,
+    # and a missing scale is then computed on the side stream, off the backward's chain.)
+    pre = (absmax_bits(xk, st), absmax_bits(dyk, st), _is_packed(xk)) if (side is not None and _WGRAD_BATCH[0] > 1 and h2) else None
+    # the half-chip split-K plan is a property of the CONFIGURATION (side stream enabled + split on), not of the stream
+    # this launch ends up on (ADVICE r5: the probe that picks the side stream is a timing measurement, and a launch that
+    # fell back to the backward's stream used to take the other plan — other bits for the same model and switches)
+    shared = _WGRAD_SHARED if (_WGRAD_STREAM[0] and _WGRAD_SHARED_ON[0]) else 0
+    dw2 = torch.empty((cout_p * taps, cin), device=dev, dtype=torch.float32) if (need_dw and cin_p != cin) else None
+    dw = None
+    if need_dw:
+        dwv = dw2.reshape(cout_p, taps, cin) if dw2 is not None else dwk
+        # logical OIHW view over OHWI memory (matches a channels_last parameter)
+        dw = _as_param_strides(dwv[:cout].reshape(cout, kh, kw, cin).permute(0, 3, 1, 2), wstr, wstr[0] == cin and wstr[1] == 1)
+    db = dbk[:cout] if need_db else None
+
+    def launch(st):
+        """the weight-gradient launches of this layer on stream `st` (torch's current stream when this runs)"""
+        ws = workspace(dev, ws_bytes)
+        sp = timing.span('conv_wgrad' if x3 else 'conv_wgrad_f32', cs.flops, cs.abytes, cs.scope)
+        if h2:
+            xbits, dybits, x_pk = pre if pre is not None else (absmax_bits(xk, st), absmax_bits(dyk, st), _is_packed(xk))
+            if side is not None:     # (slices of a pooled buffer of the main stream: keep the pool block until this has run)
+                _wgrad_hold(xbits, dybits)
+            xw_ptr, dyw_ptr, flags, _keep = _wgrad_f16x2_operands(cs, dk, xk, dyk, xbits, dybits, x_pk, dy_pk, need_db, st)
+            _launch_wgrad(dk, xw_ptr, dyw_ptr, dwk, dbk, ws, ws_bytes, st, scales=(xbits, dybits), flags=flags | shared)
+        else:
+            _launch_wgrad(dk, xk.data_ptr(), dyk.data_ptr(), dwk, dbk, ws, ws_bytes, st, x3=x3)
+        timing.stop(sp)
+        if dw2 is not None:
+            _C.call('evk_unpad_channels', dwk.data_ptr(), dw2.data_ptr(), cout_p * taps, cin_p, cin, st)
+
+    if side is None:
+        launch(st)
+        return dw, db
+    # the weight gradient beside the rest of the backward (see _WGRAD_STREAM above).  Its launches are QUEUED and
+    # issued in batches: one fork event, one switch of torch's current stream and back per batch instead of per
+    # layer (host time), and a captured step has a handful of edges between its two branches instead of 2 x 53
+    _wgrad_hold(xk, dyk, dwk, dbk, dw2)
+    _WGRAD_QUEUE.setdefault(dev, []).append(launch)
+    if need_dw:              # what AccumulateGrad has to store as it is (checked at the end of the pass)
+        _WGRAD_OWNED[id(cs.weight)] = (cs.weight, dw.untyped_storage().data_ptr())
+    if need_db:
+        _WGRAD_OWNED[id(cs.bias_leaf)] = (cs.bias_leaf, db.untyped_storage().data_ptr())
+    if len(_WGRAD_QUEUE.get(dev, ())) >= _WGRAD_BATCH[0]:
+        flush_wgrad_queue(dev)
+    return dw, db
 
 
 class _Conv2dFn(Function):
@@ -448,11 +458,9 @@ class _Conv2dFn(Function):
         y, cs = _conv_forward(x, weight, bias, stride, padding, dilation, relu, want_stats)
         if any(ctx.needs_input_grad):
             _note_param_use(weight, bias)
-        ctx.cs = cs
-        ctx.slot = slot
+        ctx.cs, ctx.slot = cs, slot
         ctx.save_for_backward(*_stash([cs]))
-        _BN_HANDOFF[0] = cs.bn_parts      # picked up by conv2d() right after apply (same thread, no autograd in between)
-        cs.bn_parts = None
+        _BN_HANDOFF[0], cs.bn_parts = cs.bn_parts, None      # picked up by _apply_with_parts() right after apply
         return y
 
     @staticmethod
@@ -460,13 +468,8 @@ class _Conv2dFn(Function):
     def backward(ctx, dy):
         cs = ctx.cs
         _unstash([cs], ctx.saved_tensors)
-        acc = None
-        if ctx.slot is not None:     # a later consumer's gradient of x, parked by _SlotOutFn: summed in the epilogue below
-            ctx.slot.consumed = True
-            acc, ctx.slot.grad = ctx.slot.grad, None
+        acc = _take_slot(ctx.slot, ctx.needs_input_grad[0])     # summed in the data-gradient epilogue below
         try:
-            if acc is not None and not ctx.needs_input_grad[0]:
-                acc = None
             dx, dw, db = _conv_backward(cs, dy, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                         cs.has_bias and ctx.needs_input_grad[2], accum=acc)
         finally:
@@ -477,11 +480,26 @@ class _Conv2dFn(Function):
 _BN_HANDOFF = [None, None]   # statistics records of the convolution(s) that just ran: [main, shortcut]
 
 
-def _attach_parts(y, parts):
-    """BatchNorm partial statistics ride on the tensor object to the BatchNorm that consumes it next."""
-    if parts is not None:
-        y._evk_bn_parts = parts
-    return y
+def _apply_with_parts(fn, *args):
+    """fn.apply(*args) between two clears of _BN_HANDOFF (same thread, no autograd in between); the statistics records its
+    forward left there ride on the output tensor(s) (`_evk_bn_parts`) to the BatchNorm that takes them (`_base._take_parts`)"""
+    _BN_HANDOFF[0] = _BN_HANDOFF[1] = None
+    out = fn.apply(*args)
+    for t, parts in zip(out if isinstance(out, tuple) else (out,), _BN_HANDOFF):
+        if parts is not None:
+            t._evk_bn_parts = parts
+    _BN_HANDOFF[0] = _BN_HANDOFF[1] = None
+    return out
+
+
+def _take_slot(slot, need_dx):
+    """The gradient of x a later consumer parked in `slot` (_SlotOutFn: that consumer's backward ran first), taken out of
+    it; None without a slot, or where x wants no gradient."""
+    if slot is None:
+        return None
+    slot.consumed = True
+    g, slot.grad = slot.grad, None
+    return g if need_dx else None
 
 
 class _GroupDenseFn(Function):
@@ -528,15 +546,13 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, relu=False, bn
     gradient is parked there (backward runs it first) and added inside this convolution's data-gradient epilogue."""
     _require_cuda(x, 'conv2d')
     x = as_nhwc(x, 'conv2d')
-    _BN_HANDOFF[0] = None
     if grad_slot is not None:
         if x.shape[1] % 8 or not _planes_math() or not (torch.is_grad_enabled() and x.requires_grad) or grad_slot.claimed:
             grad_slot = None        # (no accumulate epilogue on this path, or nothing to differentiate)
         else:
             grad_slot.claimed = True
-    y = _Conv2dFn.apply(x, weight, bias, _pair(stride), _pair(padding), _pair(dilation), bool(relu), bool(bn_stats), grad_slot)
-    parts, _BN_HANDOFF[0] = _BN_HANDOFF[0], None
-    return _attach_parts(y, parts)
+    return _apply_with_parts(_Conv2dFn, x, weight, bias, _pair(stride), _pair(padding), _pair(dilation), bool(relu),
+                             bool(bn_stats), grad_slot)
 
 
 class GradSlot:
@@ -596,18 +612,15 @@ class _ConvForkFn(Function):
         y, cs = _conv_forward(x, w_main, b_main, *cfg_main, False, want_stats[0])
         if any(ctx.needs_input_grad):
             _note_param_use(w_main, b_main, w_short, b_short)
-        ctx.cs_main = cs
-        ctx.slot = slot
-        _BN_HANDOFF[0], _BN_HANDOFF[1] = cs.bn_parts, None
-        cs.bn_parts = None
+        ctx.cs_main, ctx.slot = cs, slot
+        _BN_HANDOFF[0], _BN_HANDOFF[1], cs.bn_parts = cs.bn_parts, None, None
         if w_short is None:
             ctx.cs_short = None
             ctx.save_for_backward(*_stash([cs]))
             return y, x.view_as(x)
         ys, css = _conv_forward(x, w_short, b_short, *cfg_short, False, want_stats[1])
         ctx.cs_short = css
-        _BN_HANDOFF[1] = css.bn_parts
-        css.bn_parts = None
+        _BN_HANDOFF[1], css.bn_parts = css.bn_parts, None
         ctx.save_for_backward(*_stash([cs, css]))
         return y, ys
 
@@ -624,38 +637,29 @@ class _ConvForkFn(Function):
     @staticmethod
     def _backward(ctx, dy, dshort):
         from .pointwise import add      # (pointwise imports this module)
-        need_dx = ctx.needs_input_grad[0]
-        dws = dbs = None
-        acc = None
-        slot_g = None
-        if ctx.slot is not None:   # a later consumer's gradient of x, parked by _SlotOutFn (the head ran first)
-            ctx.slot.consumed = True
-            slot_g, ctx.slot.grad = ctx.slot.grad, None
-            if not need_dx:
-                slot_g = None
-        acc_bits = None
-        if ctx.cs_short is None:
+        cm, cshort, need = ctx.cs_main, ctx.cs_short, ctx.needs_input_grad
+        need_dx, need_m = need[0], (need[1], cm.has_bias and need[3])       # need_m / need_s: (dw, db) wanted of each branch
+        need_s = (need[2], cshort.has_bias and need[4]) if cshort is not None else None
+        dws = dbs = acc = acc_bits = None
+        slot_g = _take_slot(ctx.slot, need_dx)      # (the head ran first)
+        if cshort is None:
             acc = dshort  # gradient of the identity shortcut (possibly unmasked, with the block's ReLU bits)
             acc_bits = _lazy_bits(acc) if acc is not None else None
-        elif dshort is not None and dy is not None and need_dx and _sparse_dgrad(ctx.cs_short):
+        elif dshort is not None and dy is not None and need_dx and _sparse_dgrad(cshort):
             # strided 1x1 shortcut: the main branch's (dense) data gradient first, the shortcut's one-pixel-in-four
             # contribution accumulated into it in place — no zero fill / copy of the whole tensor for the other three
-            dx, dw, db = _conv_backward(ctx.cs_main, dy, True, ctx.needs_input_grad[1],
-                                        ctx.cs_main.has_bias and ctx.needs_input_grad[3], accum=slot_g)
-            dx, dws, dbs = _conv_backward(ctx.cs_short, dshort, True, ctx.needs_input_grad[2],
-                                          ctx.cs_short.has_bias and ctx.needs_input_grad[4], accum=dx, inplace=True)
+            dx, dw, db = _conv_backward(cm, dy, True, *need_m, accum=slot_g)
+            dx, dws, dbs = _conv_backward(cshort, dshort, True, *need_s, accum=dx, inplace=True)
             return dx, dw, dws, db, dbs, None, None, None, None
         elif dshort is not None:
-            acc, dws, dbs = _conv_backward(ctx.cs_short, dshort, need_dx, ctx.needs_input_grad[2],
-                                           ctx.cs_short.has_bias and ctx.needs_input_grad[4], accum=slot_g)
+            acc, dws, dbs = _conv_backward(cshort, dshort, need_dx, *need_s, accum=slot_g)
             slot_g = None
         if slot_g is not None:     # the shortcut convolution did not run: plain sum
             acc, acc_bits = (slot_g if acc is None else add(materialize_lazy(acc), slot_g)), None
         if dy is None:   # only the second branch reached the loss
             return materialize_lazy(acc), None, dws, None, dbs, None, None, None, None
-        dx, dw, db = _conv_backward(ctx.cs_main, dy, need_dx, ctx.needs_input_grad[1],
-                                    ctx.cs_main.has_bias and ctx.needs_input_grad[3],
-                                    accum=acc if need_dx else None, accum_bits=acc_bits if need_dx else None)
+        dx, dw, db = _conv_backward(cm, dy, need_dx, *need_m, accum=acc if need_dx else None,
+                                    accum_bits=acc_bits if need_dx else None)
         return dx, dw, dws, db, dbs, None, None, None, None
 
 
@@ -669,26 +673,31 @@ def conv2d_fork(x, conv_main, conv_short=None, bn_stats=(False, False)):
                                                 conv_short.padding, conv_short.dilation)
         return y, s
     cfg_m = (_pair(conv_main.stride), _pair(conv_main.padding), _pair(conv_main.dilation))
-    _BN_HANDOFF[0] = _BN_HANDOFF[1] = None
     if conv_short is None:
-        y, s = _ConvForkFn.apply(x, conv_main.weight, None, conv_main.bias, None, cfg_m, None, None,
+        return _apply_with_parts(_ConvForkFn, x, conv_main.weight, None, conv_main.bias, None, cfg_m, None, None,
                                  (bool(bn_stats[0]), False))
-        parts, _BN_HANDOFF[0] = _BN_HANDOFF[0], None
-        return _attach_parts(y, parts), s
     cfg_s = (_pair(conv_short.stride), _pair(conv_short.padding), _pair(conv_short.dilation))
     slot = getattr(x, '_evk_grad_slot', None)
     if slot is not None and not slot.claimed and torch.is_grad_enabled() and x.requires_grad:
         slot.claimed = True   # this node will add the parked gradient inside its shortcut data-gradient launch
     else:
         slot = None
-    y, s = _ConvForkFn.apply(x, conv_main.weight, conv_short.weight, conv_main.bias, conv_short.bias, cfg_m, cfg_s, slot,
-                             (bool(bn_stats[0]), bool(bn_stats[1])))
-    pm, ps = _BN_HANDOFF
-    _BN_HANDOFF[0] = _BN_HANDOFF[1] = None
-    return _attach_parts(y, pm), _attach_parts(s, ps)
+    return _apply_with_parts(_ConvForkFn, x, conv_main.weight, conv_short.weight, conv_main.bias, conv_short.bias, cfg_m, cfg_s,
+                             slot, (bool(bn_stats[0]), bool(bn_stats[1])))
 
 
 # ------------------------------------------------------------------------------------ transposed convolution
+def _x3_planes(weight, w_ohwi, d, for_dgrad, st, dev):
+    """Pointer of the three-term planes of `weight` (the transposed convolution runs on the `_x3` entries under every plane
+    arithmetic, so not `_base._weight_planes`, which follows the mode): from the cache, else split into the workspace."""
+    pl_ptr = weight_planes.planes_for(weight, w_ohwi, d, for_dgrad, st)
+    if pl_ptr is not None:
+        return pl_ptr
+    planes = workspace(dev, _C.load().evk_conv2d_split_weight_bytes(ctypes.byref(d), for_dgrad))
+    _C.call('evk_conv2d_split_weight', ctypes.byref(d), w_ohwi.data_ptr(), for_dgrad, planes.data_ptr(), st)
+    return planes.data_ptr()
+
+
 class _ConvTranspose2dFn(Function):
     """nn.ConvTranspose2d = the adjoint of the convolution C that reads the same weight memory as OHWI (include/ever_hip.h,
     evk_conv_transpose2d_*): forward on the residue-class data-gradient kernel, input gradient on the forward kernel,
@@ -708,9 +717,8 @@ class _ConvTranspose2dFn(Function):
         # descriptor of C: its input is this operator's output
         d = _C.ConvDesc(n, ho, wo, cout_t, h, w, cin_t, kh, kw, stride[0], stride[1], padding[0], padding[1],
                         dilation[0], dilation[1])
-        chk_h = (ho + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-        chk_w = (wo + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-        if (chk_h, chk_w) != (h, w) or ho <= 0 or wo <= 0:
+        chk = (_conv_out(ho, kh, stride[0], padding[0], dilation[0]), _conv_out(wo, kw, stride[1], padding[1], dilation[1]))
+        if chk != (h, w) or ho <= 0 or wo <= 0:
             raise ValueError('conv_transpose2d: output_padding must be smaller than stride or dilation')
         dev, st = x.device, _stream()
         w_ohwi = _weight_ohwi(weight.detach())      # [Cin_t][kh][kw][Cout_t]
@@ -719,18 +727,13 @@ class _ConvTranspose2dFn(Function):
         flops = 2.0 * n * h * w * cin_t * cout_t * kh * kw
         sp = timing.span('conv_igemm' if x3 else 'conv_igemm_f32', flops, 4.0 * (x.numel() + y.numel() + weight.numel()))
         if x3:
-            pl_ptr = weight_planes.planes_for(weight, w_ohwi, d, 1, st)
-            if pl_ptr is None:
-                planes = workspace(dev, _C.load().evk_conv2d_split_weight_bytes(ctypes.byref(d), 1))
-                _C.call('evk_conv2d_split_weight', ctypes.byref(d), w_ohwi.data_ptr(), 1, planes.data_ptr(), st)
-                pl_ptr = planes.data_ptr()
-            _C.call('evk_conv_transpose2d_fwd_x3', ctypes.byref(d), x.data_ptr(), pl_ptr, _ptr(bias), y.data_ptr(), st)
+            _C.call('evk_conv_transpose2d_fwd_x3', ctypes.byref(d), x.data_ptr(), _x3_planes(weight, w_ohwi, d, 1, st, dev),
+                    _ptr(bias), y.data_ptr(), st)
         else:
             wt = torch.empty((cout_t, kh * kw, cin_t), device=dev, dtype=torch.float32)
             _C.call('evk_conv2d_pack_dgrad_weight', ctypes.byref(d), w_ohwi.data_ptr(), wt.data_ptr(), st)
             _C.call('evk_conv_transpose2d_fwd', ctypes.byref(d), x.data_ptr(), wt.data_ptr(), _ptr(bias), y.data_ptr(), st)
-        if sp is not None:
-            sp.stop()
+        timing.stop(sp)
         ctx.desc, ctx.flops, ctx.has_bias, ctx.w_stride = d, flops, bias is not None, tuple(weight.stride())
         ctx.save_for_backward(x, weight)
         return y
@@ -751,16 +754,11 @@ class _ConvTranspose2dFn(Function):
             x3 = x3m and cout_t % 8 == 0
             sp = timing.span('conv_igemm' if x3 else 'conv_igemm_f32', ctx.flops, 4.0 * (x.numel() + gy.numel()))
             if x3:
-                pl_ptr = weight_planes.planes_for(weight, w_ohwi, d, 0, st)
-                if pl_ptr is None:
-                    planes = workspace(dev, _C.load().evk_conv2d_split_weight_bytes(ctypes.byref(d), 0))
-                    _C.call('evk_conv2d_split_weight', ctypes.byref(d), w_ohwi.data_ptr(), 0, planes.data_ptr(), st)
-                    pl_ptr = planes.data_ptr()
-                _C.call('evk_conv_transpose2d_dgrad_x3', ctypes.byref(d), gy.data_ptr(), pl_ptr, dx.data_ptr(), st)
+                _C.call('evk_conv_transpose2d_dgrad_x3', ctypes.byref(d), gy.data_ptr(), _x3_planes(weight, w_ohwi, d, 0, st, dev),
+                        dx.data_ptr(), st)
             else:
                 _C.call('evk_conv_transpose2d_dgrad', ctypes.byref(d), gy.data_ptr(), w_ohwi.data_ptr(), dx.data_ptr(), st)
-            if sp is not None:
-                sp.stop()
+            timing.stop(sp)
         need_dw, need_db = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         if need_dw or need_db:
             ws_bytes = _C.load().evk_conv_transpose2d_wgrad_workspace_bytes(ctypes.byref(d), 1 if x3m else 0)
@@ -770,12 +768,10 @@ class _ConvTranspose2dFn(Function):
             sp = timing.span('conv_wgrad' if x3m else 'conv_wgrad_f32', ctx.flops, 4.0 * (x.numel() + gy.numel()))
             _C.call('evk_conv_transpose2d_wgrad_x3' if x3m else 'evk_conv_transpose2d_wgrad', ctypes.byref(d), x.data_ptr(),
                     gy.data_ptr(), _ptr(dwk), _ptr(db), ws.data_ptr(), ws_bytes, st)
-            if sp is not None:
-                sp.stop()
+            timing.stop(sp)
             if need_dw:
-                dw = dwk.reshape(cin_t, kh, kw, cout_t).permute(0, 3, 1, 2)   # logical [Cin_t, Cout_t, kh, kw]
-                if kh * kw == 1 and dw.stride() != ctx.w_stride and ctx.w_stride[1] == 1:
-                    dw = dw.as_strided(dw.shape, ctx.w_stride)
+                # logical [Cin_t, Cout_t, kh, kw]
+                dw = _as_param_strides(dwk.reshape(cin_t, kh, kw, cout_t).permute(0, 3, 1, 2), ctx.w_stride, ctx.w_stride[1] == 1)
         return dx, dw, db, None, None, None, None
 
 
@@ -812,22 +808,13 @@ class _StemConvFn(Function):
         flops = 2.0 * n * (h // 2) * (w // 2) * cout * c * 49     # algorithmic: the 7x7 taps, not the 4x4x16 padding
         nbytes = 4.0 * (x.numel() + y.numel() + weight.numel())
         sp = timing.span('conv_igemm', flops, nbytes)
+        # BatchNorm statistics of the stem's output from the epilogue as well (the largest map of the network): f16x2 only
+        stats = wabs_ptr is not None and want_stats and _BN_EPILOGUE and cout % 4 == 0
+        parts, cap = _stats_request(d, dev) if stats else (None, 0)
+        nparts = _launch_forward(d, xs.data_ptr(), xbits, pl_ptr, wabs_ptr, None, y, 0, st, parts, cap)
         if wabs_ptr is not None:
-            # BatchNorm statistics of the stem's output from the epilogue as well (the largest map of the network)
-            parts, cap, nparts = None, 0, ctypes.c_int32(0)
-            if want_stats and _BN_EPILOGUE and cout % 4 == 0:
-                cap = int(_C.load().evk_conv2d_stats_max_parts(ctypes.byref(d)))
-                parts = torch.empty((cap * 3 * cout,), device=dev, dtype=torch.float32)
-            _C.call('evk_conv2d_fwd_f16x2', ctypes.byref(d), xs.data_ptr(), xbits.data_ptr(), pl_ptr, wabs_ptr, None, None,
-                    y.data_ptr(), 0, _ptr(parts), cap, ctypes.byref(nparts), None, st)
-            _BN_HANDOFF[0] = (parts, int(nparts.value)) if nparts.value > 0 else None
-        elif get_conv_math() == 'bf16':
-            _C.call('evk_conv2d_fwd_bf16', ctypes.byref(d), xs.data_ptr(), pl_ptr, None, y.data_ptr(), 0, None, 0,
-                    ctypes.byref(ctypes.c_int32(0)), st)
-        else:
-            _C.call('evk_conv2d_fwd_x3', ctypes.byref(d), xs.data_ptr(), pl_ptr, None, y.data_ptr(), 0, st)
-        if sp is not None:
-            sp.stop()
+            _BN_HANDOFF[0] = (parts, nparts) if nparts > 0 else None
+        timing.stop(sp)
         ctx.desc, ctx.flops, ctx.nbytes, ctx.cin, ctx.scope = d, flops, nbytes, c, timing.current_scope()
         ctx.w_stride = tuple(weight.stride())
         ctx.save_for_backward(xs)
@@ -840,22 +827,13 @@ class _StemConvFn(Function):
         d, c = ctx.desc, ctx.cin
         dev, st = xs.device, _stream()
         dy = as_nhwc(dy, 'stem.backward')
-        lib = _C.load()
-        ws_bytes = lib.evk_conv2d_wgrad_x3_workspace_bytes(ctypes.byref(d))
+        ws_bytes = _C.load().evk_conv2d_wgrad_x3_workspace_bytes(ctypes.byref(d))
         ws = workspace(dev, ws_bytes)
         dw4 = torch.empty((d.Cout, 4, 4, 16), device=dev, dtype=torch.float32)
-        h2 = _f16x2()
-        if h2:
-            xbits, dybits = absmax_bits(xs, st), absmax_bits(dy, st)
+        scales = (absmax_bits(xs, st), absmax_bits(dy, st)) if _f16x2() else None
         sp = timing.span('conv_wgrad', ctx.flops, ctx.nbytes, ctx.scope)
-        if h2:
-            _C.call('evk_conv2d_wgrad_f16x2', ctypes.byref(d), xs.data_ptr(), xbits.data_ptr(), dy.data_ptr(), dybits.data_ptr(),
-                    dw4.data_ptr(), None, ws.data_ptr(), ws_bytes, st)
-        else:
-            _C.call(_entry('evk_conv2d_wgrad_x3'), ctypes.byref(d), xs.data_ptr(), dy.data_ptr(), dw4.data_ptr(), None,
-                    ws.data_ptr(), ws_bytes, st)
-        if sp is not None:
-            sp.stop()
+        _launch_wgrad(d, xs.data_ptr(), dy.data_ptr(), dw4, None, ws, ws_bytes, st, scales=scales)
+        timing.stop(sp)
         dw7 = torch.empty((d.Cout, 7, 7, c), device=dev, dtype=torch.float32)
         _C.call('evk_stem_s2d_weight_bwd', dw4.data_ptr(), dw7.data_ptr(), d.Cout, c, st)
         return None, dw7.permute(0, 3, 1, 2), None               # logical OIHW over OHWI memory, as the parameter
@@ -873,10 +851,7 @@ def stem_conv_applicable(x, conv):
 
 def stem_conv7x7s2(x, weight, bn_stats=False):
     _require_cuda(x, 'stem_conv7x7s2')
-    _BN_HANDOFF[0] = None
-    y = _StemConvFn.apply(x, weight, bool(bn_stats))
-    parts, _BN_HANDOFF[0] = _BN_HANDOFF[0], None
-    return _attach_parts(y, parts)
+    return _apply_with_parts(_StemConvFn, x, weight, bool(bn_stats))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

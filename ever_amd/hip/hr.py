@@ -12,7 +12,7 @@ from . import weight_planes
 from .workspace import workspace
 from ._base import (
     HipPathError, _amax_out, _amax_zeroed, _f16x2, _is_packed, _mark_packed, _note_amax, _ptr, _require_cuda, _stream,
-    _timed_call, as_nhwc, empty_nhwc, materialize_lazy,
+    _take_parts, _timed_call, as_nhwc, empty_nhwc, materialize_lazy,
 )
 
 __all__ = ['hr_fuse', 'bilinear_concat', 'hr_fuse_stats']
@@ -151,7 +151,7 @@ def hr_fuse(terms):
             if not _fusable_bn(bn) or t.shape[1] % 4 or (batch and (parts is None or parts[1] <= 0)):
                 t = as_nhwc(bn(t), 'hr_fuse')       # layer by layer: the module's own forward (and hooks)
             elif batch:
-                del t._evk_bn_parts
+                _take_parts(t)
                 track = bn.track_running_stats and bn.running_mean is not None
                 if track:
                     weight_planes.note_running_stats_changed()

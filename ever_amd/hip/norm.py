@@ -13,7 +13,8 @@ from . import timing, weight_planes
 from .workspace import workspace
 from ._base import (  # noqa: F401
     HipPathError, _AMAX_HANDOFF, _LAZY_RES, _PACKED, _RELU_BITS, _affine_grads, _amax_out, _amax_zeroed, _dx_scale, _f16x2,
-    _hand_scale, _inherit_amax, _lazy_bits, _mark_packed, _note_amax, _ptr, _require_cuda, _stream, _take_handoff, _timed_call,
+    _hand_scale, _inherit_amax, _lazy_bits, _mark_packed, _note_amax, _ptr, _require_cuda, _stream, _take_handoff, _take_parts,
+    _timed_call,
     as_nhwc, empty_nhwc, is_nhwc, materialize_lazy, observers_active, relu_bits_stats,
 )
 
@@ -142,9 +143,7 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, training, momentu
     if residual is not None:
         residual = as_nhwc(residual, 'batch_norm.residual')
     use_batch_stats = training or running_mean is None
-    parts = getattr(x, '_evk_bn_parts', None) if use_batch_stats else None
-    if parts is not None:
-        del x._evk_bn_parts
+    parts = _take_parts(x) if use_batch_stats else None
     _AMAX_HANDOFF[0] = None
     if use_batch_stats and running_mean is not None:
         weight_planes.note_running_stats_changed()
@@ -241,7 +240,8 @@ def batch_norm_act_dual(za, bn_a, zb, bn_b):
     for bn in (bn_a, bn_b):
         if not bn.training or bn.momentum is None or za.shape[0] * za.shape[2] * za.shape[3] == 1:
             return None
-    del za._evk_bn_parts, zb._evk_bn_parts
+    _take_parts(za)
+    _take_parts(zb)
     args = []
     for bn in (bn_b, bn_a):     # (the shortcut's bookkeeping first, as its own layer call would have come first)
         if bn.track_running_stats and bn.num_batches_tracked is not None:
@@ -318,7 +318,7 @@ def batch_norm_relu_max_pool(x, weight, bias, running_mean, running_var, momentu
     if parts is None or not _STEM_POOL or c % 4 or n * h * w * (c // 4) >= 2 ** 31:
         from .pointwise import max_pool3x3s2      # (pointwise imports this module's neighbours)
         return max_pool3x3s2(batch_norm_act(x, weight, bias, running_mean, running_var, True, momentum, eps, relu=True))
-    del x._evk_bn_parts
+    _take_parts(x)
     _AMAX_HANDOFF[0] = None
     if running_mean is not None:
         weight_planes.note_running_stats_changed()

@@ -13,7 +13,7 @@ from . import timing, weight_planes
 from .workspace import workspace
 from ._base import (  # noqa: F401
     HipPathError, _AMAX_HANDOFF, _affine_grads, _amax_zeroed, _conv_out, _dx_scale, _hand_scale, _inherit_amax, _note_amax, _ptr,
-    _require_cuda, _same_shape_fake, _stream, _take_handoff, _timed_call, as_nhwc, empty_nhwc,
+    _require_cuda, _same_shape_fake, _stream, _take_handoff, _take_parts, _timed_call, as_nhwc, empty_nhwc,
 )
 from .streams import (  # noqa: F401
     _note_param_use,
@@ -332,7 +332,8 @@ def fs_relation_bn(scene, zc, zf, bn_c, bn_f):
     pc, pf = getattr(zc, '_evk_bn_parts', None), getattr(zf, '_evk_bn_parts', None)
     if pc is None or pf is None or pc[1] <= 0 or pf[1] <= 0 or zc.shape != zf.shape or zc.shape[1] % 4 or zc.shape[1] > 448:
         return None
-    del zc._evk_bn_parts, zf._evk_bn_parts
+    _take_parts(zc)
+    _take_parts(zf)
     n, c, h, w = zc.shape
     scene = as_nhwc(scene.reshape(n, c, 1, 1), 'fs_relation.scene')
     weight_planes.note_running_stats_changed()
@@ -419,7 +420,7 @@ def bn_relu_dot(z, bn, conv):
     if (parts is None or parts[1] <= 0 or conv.weight.shape[1] != c
             or not bn_relu_dot_admits(c, k, conv.weight.shape[2:])):
         return None      # (the kernel's register / LDS budget: csrc/bn_dot.hip evk_bn_relu_dot_bwd)
-    del z._evk_bn_parts
+    _take_parts(z)
     weight_planes.note_running_stats_changed()
     if torch.is_grad_enabled():
         _note_param_use(conv.weight, conv.bias)

@@ -170,3 +170,9 @@ class _Span:
 def span(family, flops, nbytes=0.0, sc=None):
     """Start timing one launch (algorithmic FLOPs and bytes attached); None when no timer is active."""
     return _Span(family, flops, nbytes, _scope if sc is None else sc) if _active is not None else None
+
+
+def stop(sp):
+    """end a span() — None while no KernelTimer is active"""
+    if sp is not None:
+        sp.stop()

@@ -229,9 +229,8 @@ def _folded_fake(x, weight, bias, residual, stride, padding, dilation, relu):
         cout, kh, kw = weight.shape[0], weight.shape[2], weight.shape[3]
     else:
         cout, kh, kw, _ = weight.shape
-    ho = (x.shape[2] + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    wo = (x.shape[3] + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    return HF._oplib.nhwc_like(x, x.shape[0], cout, ho, wo)
+    return HF._oplib.nhwc_like(x, x.shape[0], cout, HF._conv_out(x.shape[2], kh, stride[0], padding[0], dilation[0]),
+                               HF._conv_out(x.shape[3], kw, stride[1], padding[1], dilation[1]))
 
 
 _folded_conv_op = HF._oplib.traceable(

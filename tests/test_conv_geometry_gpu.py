@@ -112,12 +112,10 @@ def _reference(c, bf16=False):
 def routes(lib, c, planes):
     """(forward kernel, [data-gradient kernel per residue class, '' = no launch]) evk_conv2d_route names for the descriptor
     the Python layer builds: hip/conv.py pads Cin and Cout to multiples of 4 (`_pad4`) and, under the split arithmetics, a Cout
-    below 8 to 8 (`narrow8`, which needs an unpadded Cin) — restated here with conv.py's own `_pad4`"""
+    below 8 to 8 (`narrow8`, which needs an unpadded Cin) — by conv.py's own rule, `conv_channel_padding`"""
     from ever_amd import _C
-    from ever_amd.hip.conv import _pad4
-    cin = _pad4(c['cin'])
-    narrow8 = planes != 0 and cin == c['cin'] and c['cout'] % 8 != 0 and c['cout'] < 8
-    cout = 8 if narrow8 else _pad4(c['cout'])
+    from ever_amd.hip.conv import conv_channel_padding
+    cin, cout, _ = conv_channel_padding(c['cin'], c['cout'], planes != 0)
     (kh, kw), (sh, sw), (ph, pw), (dh, dw) = c['k'], c['s'], c['p'], c['dil']
     ho, wo = (c['h'] + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (c['w'] + 2 * pw - dw * (kw - 1) - 1) // sw + 1
     d = _C.ConvDesc(c['n'], c['h'], c['w'], cin, ho, wo, cout, kh, kw, sh, sw, ph, pw, dh, dw)
