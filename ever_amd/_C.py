@@ -206,6 +206,13 @@ SIGNATURES = {
     'evk_depthwise_bwd': (c_int, [_DP, P, P, P, P, P, P, P, P, c_size_t, P]),
     'evk_broadcast_hw': (c_int, [P, P, c_i32, c_i64, c_i32, P]),
     'evk_sum_hw': (c_int, [P, P, c_i32, c_i64, c_i32, P]),
+    'evk_ln_plan': (c_int, [c_i64, c_i32, C.POINTER(c_i32)]),
+    'evk_ln_bwd_workspace_bytes': (c_size_t, [c_i64, c_i32]),
+    'evk_ln_fwd': (c_int, [P, P, P, c_f32, P, P, P, c_i64, c_i32, P]),
+    'evk_ln_bwd': (c_int, [P, P, P, P, P, P, P, P, c_i64, c_i32, P, c_size_t, P]),
+    'evk_scale_residual_fwd': (c_int, [P, P, P, P, P, c_i32, c_i64, c_i32, P]),
+    'evk_scale_residual_bwd_workspace_bytes': (c_size_t, [c_i32, c_i64, c_i32]),
+    'evk_scale_residual_bwd': (c_int, [P, P, P, P, P, P, c_i32, c_i64, c_i32, P, c_size_t, P]),
 }
 
 _lib = None

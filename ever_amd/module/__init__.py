@@ -1,6 +1,8 @@
 from . import loss  # noqa: F401
 from .aspp import ASPPHead, AtrousSpatialPyramidPool
 from .changestar import ChangeMixin, ChangeStarFarSeg
+from . import dinov3  # noqa: F401
+from .convnext_encoder import ConvNeXtEncoder
 from .deeplab import DeepLabV3Plus
 from .deeplabv3p_head import Deeplabv3pDecoder, Deeplabv3pHead
 from .farseg import FarSeg, FarSegPP
@@ -11,8 +13,8 @@ from .hrnet_head import HRNetHead, SimpleFusion
 from .hrnet_seg import HRNetSeg
 from ._hrnet import HighResolutionModule, HighResolutionNet
 from .fs_relation import FarSegHead, FarSegPPHead, FSRelation, FSRelationV2
-from .layers import (AdaptiveAvgPool2d, BatchNorm2d, Conv2d, ConvTranspose2d, HipSequential, MaxPool2d, ReLU, UpsamplingBilinear2d,
-                     to_hip)
+from .layers import (AdaptiveAvgPool2d, BatchNorm2d, Conv2d, ConvTranspose2d, HipSequential, LayerNorm, MaxPool2d, ReLU,
+                     UpsamplingBilinear2d, to_hip)
 from .ops import Bf16compatible, ConvBlock, ConvUpsampling, DepthwiseConv2d, PoolBlock, SeparableConv2d, SeparableConvBlock
 from .resnet import ResNetEncoder
 
@@ -22,4 +24,5 @@ __all__ = ['ResNetEncoder', 'FPN', 'AssymetricDecoder', 'FSRelation', 'FSRelatio
            'DepthwiseConv2d', 'SeparableConv2d', 'SeparableConvBlock', 'PoolBlock', 'AtrousSpatialPyramidPool', 'ASPPHead',
            'Deeplabv3pDecoder', 'Deeplabv3pHead', 'DeepLabV3Plus',
            'HighResolutionModule', 'HighResolutionNet', 'HRNetEncoder', 'SimpleFusion', 'HRNetHead', 'HRNetSeg',
-           'Fusion', 'FastNormalizedFusionConv3x3', 'NormalizedFusionConv3x3', 'BiFPN']
+           'Fusion', 'FastNormalizedFusionConv3x3', 'NormalizedFusionConv3x3', 'BiFPN',
+           'LayerNorm', 'ConvNeXtEncoder', 'dinov3']

@@ -13,7 +13,7 @@ import torch.nn as nn
 from ..hip import functional as HF
 
 __all__ = ['Conv2d', 'ConvTranspose2d', 'BatchNorm2d', 'ReLU', 'MaxPool2d', 'UpsamplingBilinear2d', 'UpsamplingNearest2d', 'AdaptiveAvgPool2d',
-           'Identity', 'Dropout', 'GELU', 'HipSequential', 'run_sequence', 'to_hip']
+           'Identity', 'Dropout', 'GELU', 'LayerNorm', 'HipSequential', 'run_sequence', 'to_hip']
 
 Identity = nn.Identity
 
@@ -204,6 +204,19 @@ class GELU(nn.GELU):
         return HN.gelu(x)
 
 
+class LayerNorm(nn.LayerNorm):
+    """nn.LayerNorm over the LAST axis of a CUDA tensor on the row kernels (HF.layer_norm; reference convnext.py:177: the
+    final norm over [N, HW + 1, C] tokens).  A normalized_shape of more than one axis has no kernel."""
+
+    def forward(self, x):
+        if len(self.normalized_shape) != 1:
+            raise NotImplementedError(f'ever_amd LayerNorm: only one normalised axis is implemented, got '
+                                      f'normalized_shape={tuple(self.normalized_shape)}')
+        if x.shape[-1] != self.normalized_shape[0]:
+            raise RuntimeError(f'ever_amd LayerNorm: last axis of {tuple(x.shape)} is not {self.normalized_shape[0]}')
+        return HF.layer_norm(x, self.weight, self.bias, self.eps, channel_dim=-1)
+
+
 def _unwrap(m):
     # reference ops.Bf16compatible wraps the upsampling module (ever/module/ops.py:152-166); the HIP
     # path is fp32 end to end so the wrapper is transparent.
@@ -257,7 +270,8 @@ class HipSequential(nn.Sequential):
 _SWAP = {
     nn.Conv2d: Conv2d, nn.ConvTranspose2d: ConvTranspose2d, nn.BatchNorm2d: BatchNorm2d, nn.ReLU: ReLU, nn.MaxPool2d: MaxPool2d,
     nn.UpsamplingBilinear2d: UpsamplingBilinear2d, nn.AdaptiveAvgPool2d: AdaptiveAvgPool2d,
-    nn.GroupNorm: GroupNorm, nn.Dropout2d: Dropout2d, nn.Dropout: Dropout, nn.GELU: GELU, nn.Sequential: HipSequential,
+    nn.GroupNorm: GroupNorm, nn.Dropout2d: Dropout2d, nn.Dropout: Dropout, nn.GELU: GELU, nn.LayerNorm: LayerNorm,
+    nn.Sequential: HipSequential,
 }
 
 

@@ -882,6 +882,39 @@ int evk_depthwise_bwd(const evk_conv_desc* d, const float* dy, const float* x, c
 int evk_broadcast_hw(const float* src, float* dst, int32_t N, int64_t HW, int32_t C, void* stream);
 int evk_sum_hw(const float* src, float* dst, int32_t N, int64_t HW, int32_t C, void* stream);
 
+/* ------------------------------------------------------------------ row LayerNorm, layer-scale residual --- */
+/* LayerNorm over the C floats of a row of a dense [R][C] fp32 matrix: ConvNeXt's LayerNorm in both data formats (a
+ * logical-NCHW map is NHWC memory: one row per pixel) and nn.LayerNorm(C) on tokens — reference
+ * dinov3/models/convnext.py:86-113,177,224.  y = (x - mean) * rstd * gamma + beta, biased variance,
+ * rstd = 1 / sqrt(var + eps); the variance is the sum of squared residuals, never E[x^2] - mean^2.  gamma / beta may be
+ * NULL (no affine), save_mean / save_rstd [R] may be NULL (inference).  Scope: C % 4 == 0, 4 <= C <= 2048, R >= 1, dense
+ * rows, 16-byte aligned pointers; anything else returns EVK_E_INVALID / EVK_E_UNSUPPORTED before a launch.
+ * evk_ln_plan (host only): out = {lanes per row L (a power of two <= 64), 16-byte columns per lane (L * columns >= C / 4 >
+ * L * (columns - 1)), rows per workgroup per trip, workgroups (bounded whatever R is)}; it refuses what the launches refuse. */
+int evk_ln_plan(int64_t R, int32_t C, int32_t* out /*[4]*/);
+/* Host only: bytes of the per-workgroup dgamma / dbeta records of evk_ln_bwd, [workgroups][2][C] floats (0 out of scope). */
+size_t evk_ln_bwd_workspace_bytes(int64_t R, int32_t C);
+int evk_ln_fwd(const float* x, const float* gamma, const float* beta, float eps, float* y, float* save_mean,
+               float* save_rstd, int64_t R, int32_t C, void* stream);
+/* Gradients of evk_ln_fwd in one pass over dy and x: dx, dgamma [C], dbeta [C], each may be NULL (not all three).  The
+ * workspace is needed for dgamma / dbeta only; its records are summed in a fixed order (no atomics: same bits every run). */
+int evk_ln_bwd(const float* dy, const float* x, const float* save_mean, const float* save_rstd, const float* gamma,
+               float* dx, float* dgamma, float* dbeta, int64_t R, int32_t C, void* workspace, size_t workspace_bytes,
+               void* stream);
+/* The tail of a ConvNeXt block, input + drop_path(gamma * x) (convnext.py:20-28,78-82), on [N][HW][C] fp32:
+ * y = a + (s[n] * gamma[c]) * z with every product and the sum rounded on its own, in that order.  gamma [C] may be NULL
+ * (no layer scale), sample_scale s [N] may be NULL (eval mode, rate 0); it holds floor(keep + u) / keep per sample.
+ * Same scope and thread plan as evk_ln_* (evk_ln_plan(N * HW, C)). */
+int evk_scale_residual_fwd(const float* a, const float* z, const float* gamma, const float* sample_scale, float* y,
+                           int32_t N, int64_t HW, int32_t C, void* stream);
+/* Host only: bytes of the per-workgroup dgamma records of evk_scale_residual_bwd, [workgroups][C] floats (0 out of scope). */
+size_t evk_scale_residual_bwd_workspace_bytes(int32_t N, int64_t HW, int32_t C);
+/* dz = (s[n] * gamma[c]) * dy (may be NULL), dgamma[c] = sum over n, p of s[n] * (dy * z) (may be NULL; then z and the
+ * workspace may be NULL too), summed in a fixed order.  The gradient of a is dy itself. */
+int evk_scale_residual_bwd(const float* dy, const float* z, const float* gamma, const float* sample_scale, float* dz,
+                           float* dgamma, int32_t N, int64_t HW, int32_t C, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

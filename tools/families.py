@@ -32,6 +32,8 @@ FAMILIES = (
                                                 '^relu_bits_apply', '^scale_store', '^subsample2', '^broadcast_hw', '^sum_hw', '^hr_fuse_', '^d4_', '^wfuse_', '^augment_')),
     ('depthwise', 'depthwise convolution (depthwise_fwd / depthwise_bwd / depthwise_reduce kernels: exact fp32 on the vector ALUs)',
      ('^depthwise_',)),
+    ('ln', 'row LayerNorm and layer-scale residual (ln_fwd / ln_bwd / ln_records_finalize, lscale_fwd / lscale_bwd kernels)',
+     ('^ln_', '^lscale_')),
     ('operand_prep', 'operand preparation of the f16x2 arithmetic (absmax* scale words, split_weight* planes)',
      ('^absmax', '^split_weight', '^pack_dgrad_weight', '^stem_s2d_weight', '^group_weight')),
     ('optimizer', 'fused optimizer / gradient-bucket kernels (sgd_multi, sqnorm_multi, pack_multi, clip)', ('^sgd_', '^adam_', '^sqnorm_', '^pack_multi', '^clip_', '^unpack_multi', '^scale_multi')),
