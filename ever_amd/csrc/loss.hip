@@ -1,61 +1,41 @@
-// Pixel-wise losses with ignore_index on NHWC logits / int64 labels (gfx950), forward statistics and
-// gradients.  Replaces the masked_select compaction + reductions of reference
-// ever/module/loss.py:10-17 (_masked_ignore), :26-37 (select), :40-75 (dice), :207-219 (LS-CE),
-// :229-235 (BCE) and F.cross_entropy(ignore_index=...) in user model code.
-// HBM-bound masked reductions: fp64 accumulation, per-workgroup partials then a single-workgroup
-// finalisation (fixed order => reproducible).  stats layout: [K finals][kLossBlocks x K partials].
-#include "common.hpp"
+// The scalar losses on NHWC logits (gfx950), forward statistics and gradients:
+//   * BCE, dice, CE and soft CE with ignore_index on int64 labels.  Replaces the masked_select compaction + reductions
+//     of reference ever/module/loss.py:10-17 (_masked_ignore), :26-37 (select), :40-75 (dice), :207-219 (LS-CE),
+//     :229-235 (BCE) and F.cross_entropy(ignore_index=...) in user model code;
+//   * class-probability statistics (tp, sum p, sum y per class) and their adjoint: the sufficient statistics of
+//     tversky_loss_with_logits (loss.py:78-143) and of any dice-like ratio loss;
+//   * focal losses on float targets (loss.py:158-201).
+// HBM-bound masked reductions: fp64 accumulation, per-workgroup partials, then a finalisation in a fixed order
+// (reproducible).  stats layout: [K finals][nblk x K partials].  The shared pieces are in loss_common.hpp; the
+// per-pixel losses are in loss_pixel.hip, the confusion matrix in metric.hip.
+#include "loss_common.hpp"
 
 namespace evk {
 
-constexpr int kLossBlocks = 2048;   // 256 left the 4-million-pixel losses on a quarter of the chip (62 us for 50 MB)
 constexpr int kMaxClasses = 64;
 constexpr int kDiceLdsBytes = 64 * 1024;
 constexpr int kDiceMaxClasses = kDiceLdsBytes / (256 * 2 * (int)sizeof(double));  // 16: [256][2C] doubles of the softmax path
 
-static inline int loss_grid(int64_t npix) {
-  int64_t b = (npix + 2047) / 2048;   // >= 8 pixels per thread
-  return (int)(b > kLossBlocks ? kLossBlocks : (b < 1 ? 1 : b));
-}
-
-// block reduction of K doubles held one-per-thread-per-k via LDS; thread 0 gets the result
-template <int K>
-__device__ __forceinline__ void block_reduce_store(double (&v)[K], double* out) {
-  __shared__ double red[K][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double s = wave_sum_d(v[k]);
-    if (lane == 0) red[k][wave] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) out[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-  }
-  __syncthreads();
-}
-
-// stats[k] = sum over the nblk per-workgroup partials, one workgroup per k: every thread sums a fixed strided subset,
-// the 256 sub-sums are folded through LDS in index order (reproducible; was one thread per k walking all partials)
+// the two folds of loss_common.hpp as kernels: tree = one workgroup of 256 per k, in order = one thread per k
 __global__ __launch_bounds__(256) void finalize_partials_kernel(double* stats, int K, int nblk) {
-  __shared__ double red[256];
-  const int k = blockIdx.x;
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 256) s += stats[K + (size_t)b * K + k];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) stats[k] = red[0];
+  fold_partials_tree(stats, K, nblk);
+}
+__global__ void finalize_partials_in_order_kernel(double* stats, int K, int nblk) {
+  fold_partials_in_order(stats, K, nblk);
+}
+// the loss word of a sum (scale 1: exact) or of a mean over a count the host knows
+__global__ void loss_scale_store_kernel(const double* stats, double scale, float* loss) {
+  if (threadIdx.x == 0) *loss = (float)(stats[0] * scale);  // reduction='sum': 0 for an empty selection, as aten
+}
+// ... and over the counted valid pixels: a quotient, which a product with the reciprocal would round differently
+__global__ void mean_loss_kernel(const double* stats, float* loss) {
+  if (threadIdx.x == 0) *loss = (float)(stats[0] / stats[1]);  // 0/0 -> NaN, as mean of an empty tensor
 }
 
 // ---------------------------------------------------------------- BCE with logits -----------------
 __device__ __forceinline__ float bce_term(float x, float y, float pw) {
   // aten binary_cross_entropy_with_logits: (1-y)*x + (1 + (pos_weight-1)*y) * (log1p(exp(-|x|)) + max(-x,0))
-  return (1.f - y) * x + (1.f + (pw - 1.f) * y) * (log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f));
+  return (1.f - y) * x + (1.f + (pw - 1.f) * y) * (softplus_neg_abs(x) + fmaxf(-x, 0.f));
 }
 __global__ __launch_bounds__(256) void bce_partial_kernel(const float* __restrict__ logits,
                                                           const int64_t* __restrict__ labels, int64_t npix,
@@ -70,13 +50,7 @@ __global__ __launch_bounds__(256) void bce_partial_kernel(const float* __restric
       v[1] += 1.0;
     }
   }
-  block_reduce_store<2>(v, stats + 2 + (size_t)blockIdx.x * 2);
-}
-__global__ void mean_loss_kernel(const double* stats, float* loss) {
-  if (threadIdx.x == 0) *loss = (float)(stats[0] / stats[1]);  // 0/0 -> NaN, as mean of an empty tensor
-}
-__global__ void sum_loss_kernel(const double* stats, float* loss) {
-  if (threadIdx.x == 0) *loss = (float)stats[0];               // reduction='sum': 0 for an empty selection, as aten
+  block_sum_store<2>(v, stats + 2 + (size_t)blockIdx.x * 2);
 }
 __global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ logits,
                                                       const int64_t* __restrict__ labels, int64_t npix, int64_t ignore,
@@ -84,16 +58,16 @@ __global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ 
                                                       const double* __restrict__ stats,
                                                       const float* __restrict__ grad_scale, float* __restrict__ dlogits,
                                                       int accumulate) {
-  const float k = (grad_scale ? *grad_scale : 1.f) / (sum_reduction ? 1.f : (float)stats[1]);
+  const float k = upstream_scale(grad_scale) / (sum_reduction ? 1.f : (float)stats[1]);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (int64_t)gridDim.x * 256) {
     const int64_t t = labels[i];
     float g = 0.f;
     if (t != ignore) {
-      const float p = 1.f / (1.f + expf(-logits[i]));
+      const float p = sigmoidf_(logits[i]);
       const float y = (t == 0) ? eps : (float)t - eps;
       g = ((1.f - y) - (1.f + (pw - 1.f) * y) * (1.f - p)) * k;   // pw = 1: p - y
     }
-    dlogits[i] = accumulate ? dlogits[i] + g : g;
+    store_grad(dlogits, i, g, accumulate);
   }
 }
 
@@ -109,13 +83,13 @@ __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restri
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (int64_t)gridDim.x * 256) {
       const int64_t t = labels[i];
       if (t != ignore) {
-        const float p = 1.f / (1.f + expf(-logits[i]));
+        const float p = sigmoidf_(logits[i]);
         const float y = (float)t;
         v[0] += (double)(p * y);
         v[1] += (double)p + (double)y;
       }
     }
-    block_reduce_store<2>(v, stats + 2 + (size_t)blockIdx.x * 2);
+    block_sum_store<2>(v, stats + 2 + (size_t)blockIdx.x * 2);
   } else {
     const int K = 2 * C;
     double* mine = dacc + (size_t)threadIdx.x * K;
@@ -124,13 +98,9 @@ __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restri
       const int64_t t = labels[i];
       if (t == ignore) continue;
       const float* x = logits + i * C;
-      float m = x[0];
-      for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
-      float se = 0.f;
-      for (int c = 0; c < C; ++c) se += expf(x[c] - m);
-      const float ls = logf(se);  // log p_c = (x_c - m) - ls: no rounding at the size of m (m + ls would lose a small loss)
+      const PixelSoftmax sm = pixel_softmax(x, C);
       for (int c = 0; c < C; ++c) {
-        const float p = expf((x[c] - m) - ls);  // reference: log_softmax(dim=1).exp()
+        const float p = sm.p(x[c]);
         const float y = (t == c) ? 1.f : 0.f;
         mine[c] += (double)(p * y);
         mine[C + c] += (double)p + (double)y;
@@ -168,7 +138,7 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
     int nc = 0;
     for (int k = 0; k < C; ++k) nc += (C > 1 && k == ignore_channel) ? 0 : 1;
     const double zs = stats[C + c] + (double)smooth;
-    const double gs = grad_scale ? (double)*grad_scale : 1.0;
+    const double gs = (double)upstream_scale(grad_scale);
     const bool off = (C > 1 && c == ignore_channel);
     sa[c] = off ? 0.f : (float)(-2.0 / ((double)nc * zs) * gs);
     sb[c] = off ? 0.f : (float)((2.0 * stats[c] + (double)smooth) / ((double)nc * zs * zs) * gs);
@@ -179,34 +149,28 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
     if (CT == 1) {
       float g = 0.f;
       if (t != ignore) {
-        const float p = 1.f / (1.f + expf(-logits[i]));
+        const float p = sigmoidf_(logits[i]);
         g = (sa[0] * (float)t + sb[0]) * p * (1.f - p);
       }
-      dlogits[i] = accumulate ? dlogits[i] + g : g;
+      store_grad(dlogits, i, g, accumulate);
     } else {
       const float* x = logits + i * C;
       float* d = dlogits + i * C;
       if (t == ignore) {
-        if (!accumulate)
-          for (int c = 0; c < C; ++c) d[c] = 0.f;
+        zero_grad(d, C, accumulate);
         continue;
       }
-      float m = x[0];
-      for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
-      float se = 0.f;
-      for (int c = 0; c < C; ++c) se += expf(x[c] - m);
-      const float ls = logf(se);
+      const PixelSoftmax sm = pixel_softmax(x, C);
       float dotgp = 0.f;
       for (int c = 0; c < C; ++c) {
-        const float p = expf((x[c] - m) - ls);
+        const float p = sm.p(x[c]);
         const float g = sa[c] * ((t == c) ? 1.f : 0.f) + sb[c];
         dotgp += g * p;
       }
       for (int c = 0; c < C; ++c) {
-        const float p = expf((x[c] - m) - ls);
+        const float p = sm.p(x[c]);
         const float g = sa[c] * ((t == c) ? 1.f : 0.f) + sb[c];
-        const float v = p * (g - dotgp);
-        d[c] = accumulate ? d[c] + v : v;
+        store_grad(d, c, p * (g - dotgp), accumulate);
       }
     }
   }
@@ -222,20 +186,14 @@ __global__ __launch_bounds__(256) void ce_partial_kernel(const float* __restrict
     const int64_t t = labels[i];
     if (t == ignore) continue;
     const float* x = logits + i * C;
-    float m = x[0];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
-    float se = 0.f, sx = 0.f;
-    for (int c = 0; c < C; ++c) {
-      se += expf(x[c] - m);
-      sx += x[c] - m;
-    }
-    const float ls = logf(se);
-    const float nll = (t >= 0 && t < C) ? ls - (x[t] - m) : m + ls;
+    float sx = 0.f;
+    const PixelSoftmax sm = pixel_softmax(x, C, [&](int, float xm) { sx += xm; });
+    const float nll = (t >= 0 && t < C) ? sm.ls - (x[t] - sm.m) : sm.m + sm.ls;
     v[0] += (double)nll;
     v[1] += 1.0;
-    v[2] += (double)((float)C * ls - sx);
+    v[2] += (double)((float)C * sm.ls - sx);
   }
-  block_reduce_store<3>(v, stats + 3 + (size_t)blockIdx.x * 3);
+  block_sum_store<3>(v, stats + 3 + (size_t)blockIdx.x * 3);
 }
 __global__ void ce_finish_kernel(const double* stats, int C, float eps, float* loss) {
   if (threadIdx.x != 0) return;
@@ -248,26 +206,20 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
                                                      int64_t ignore, float eps, const double* __restrict__ stats,
                                                      const float* __restrict__ grad_scale, float* __restrict__ dlogits,
                                                      int accumulate) {
-  const float k = (grad_scale ? *grad_scale : 1.f) / (float)stats[1];
+  const float k = upstream_scale(grad_scale) / (float)stats[1];
   const float k1 = (1.f - eps) * k, k2 = eps / (float)C * k;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (int64_t)gridDim.x * 256) {
     const int64_t t = labels[i];
     const float* x = logits + i * C;
     float* d = dlogits + i * C;
     if (t == ignore) {
-      if (!accumulate)
-        for (int c = 0; c < C; ++c) d[c] = 0.f;
+      zero_grad(d, C, accumulate);
       continue;
     }
-    float m = x[0];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(x[c] - m);
-    const float ls = logf(se);
+    const PixelSoftmax sm = pixel_softmax(x, C);
     for (int c = 0; c < C; ++c) {
-      const float p = expf((x[c] - m) - ls);
-      const float v = k1 * (p - ((t == c) ? 1.f : 0.f)) + k2 * ((float)C * p - 1.f);
-      d[c] = accumulate ? d[c] + v : v;
+      const float p = sm.p(x[c]);
+      store_grad(d, c, k1 * (p - ((t == c) ? 1.f : 0.f)) + k2 * ((float)C * p - 1.f), accumulate);
     }
   }
 }
@@ -282,38 +234,145 @@ __global__ __launch_bounds__(256) void soft_ce_partial_kernel(const float* __res
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (int64_t)gridDim.x * 256) {
     const float* x = logits + i * C;
     const float* t = target + i * C;
-    float m = x[0];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(x[c] - m);
-    const float ls = logf(se);
+    const PixelSoftmax sm = pixel_softmax(x, C);
     float acc = 0.f;
-    for (int c = 0; c < C; ++c) acc += t[c] * (ls - (x[c] - m));
+    for (int c = 0; c < C; ++c) acc += t[c] * (sm.ls - (x[c] - sm.m));
     v[0] += (double)acc;
   }
-  block_reduce_store<1>(v, stats + 1 + (size_t)blockIdx.x);
-}
-__global__ void soft_ce_finish_kernel(const double* stats, double inv_npix, float* loss) {
-  if (threadIdx.x == 0) *loss = (float)(stats[0] * inv_npix);
+  block_sum_store<1>(v, stats + 1 + (size_t)blockIdx.x);
 }
 __global__ __launch_bounds__(256) void soft_ce_bwd_kernel(const float* __restrict__ logits,
                                                           const float* __restrict__ target, int64_t npix, int C,
                                                           float inv_npix, const float* __restrict__ grad_scale,
                                                           float* __restrict__ dlogits) {
-  const float k = (grad_scale ? *grad_scale : 1.f) * inv_npix;
+  const float k = upstream_scale(grad_scale) * inv_npix;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (int64_t)gridDim.x * 256) {
     const float* x = logits + i * C;
     const float* t = target + i * C;
     float* d = dlogits + i * C;
-    float m = x[0];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
-    float se = 0.f, ts = 0.f;
-    for (int c = 0; c < C; ++c) {
-      se += expf(x[c] - m);
-      ts += t[c];
+    float ts = 0.f;
+    const PixelSoftmax sm = pixel_softmax(x, C, [&](int c, float) { ts += t[c]; });
+    for (int c = 0; c < C; ++c) d[c] = k * (sm.p(x[c]) * ts - t[c]);
+  }
+}
+
+// ---------------------------------------------------------------- class-probability statistics ----
+constexpr int kProbStatsMaxC = 64;
+// stats layout: [3C finals: tp[C], sp[C], sy[C]] [nblk x 3C partials]
+__global__ __launch_bounds__(256) void prob_stats_kernel(const float* __restrict__ logits,
+                                                         const int64_t* __restrict__ labels, int64_t npix, int C,
+                                                         int64_t ignore, double* __restrict__ stats) {
+  double tp[kProbStatsMaxC], sp[kProbStatsMaxC], sy[kProbStatsMaxC];
+  for (int c = 0; c < C; ++c) tp[c] = sp[c] = sy[c] = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (int64_t)gridDim.x * 256) {
+    const int64_t t = labels[i];
+    if (t == ignore) continue;
+    const float* z = logits + i * C;
+    if (C == 1) {
+      const float p = logsigmoid_prob(z[0]);
+      const double y = (double)t;
+      tp[0] += (double)p * y;
+      sp[0] += (double)p;
+      sy[0] += y;
+    } else {
+      const PixelSoftmax sm = pixel_softmax(z, C);
+      for (int c = 0; c < C; ++c) {
+        const float p = sm.p(z[c]);
+        sp[c] += (double)p;
+        if (t == c) {
+          tp[c] += (double)p;
+          sy[c] += 1.0;
+        }
+      }
     }
-    const float ls = logf(se);
-    for (int c = 0; c < C; ++c) d[c] = k * (expf((x[c] - m) - ls) * ts - t[c]);
+  }
+  double* out = stats + 3 * C + (size_t)blockIdx.x * 3 * C;
+  for (int c = 0; c < C; ++c) {
+    const double a = block_sum(tp[c]), b = block_sum(sp[c]), d = block_sum(sy[c]);
+    if (threadIdx.x == 0) {
+      out[c] = a;
+      out[C + c] = b;
+      out[2 * C + c] = d;
+    }
+  }
+}
+// dlogits for L(tp, sp): per pixel G_c = gtp[c]*y_c + gsp[c];  sigmoid: dz = G p (1-p);
+// softmax: dz_j = p_j (G_j - sum_k G_k p_k).  (sy does not depend on the logits.)
+__global__ __launch_bounds__(256) void prob_stats_bwd_kernel(const float* __restrict__ logits,
+                                                             const int64_t* __restrict__ labels, int64_t npix, int C,
+                                                             int64_t ignore, const float* __restrict__ gtp,
+                                                             const float* __restrict__ gsp, float* __restrict__ dlogits,
+                                                             int accumulate) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (int64_t)gridDim.x * 256) {
+    const int64_t t = labels[i];
+    const float* z = logits + i * C;
+    float* d = dlogits + i * C;
+    if (t == ignore) {
+      zero_grad(d, C, accumulate);
+      continue;
+    }
+    if (C == 1) {
+      const float p = logsigmoid_prob(z[0]);
+      store_grad(d, 0, (gtp[0] * (float)t + gsp[0]) * p * (1.f - p), accumulate);
+    } else {
+      const PixelSoftmax sm = pixel_softmax(z, C);
+      float dot = 0.f;
+      for (int c = 0; c < C; ++c) dot += (gsp[c] + (t == c ? gtp[c] : 0.f)) * sm.p(z[c]);
+      for (int c = 0; c < C; ++c)
+        store_grad(d, c, sm.p(z[c]) * ((gsp[c] + (t == c ? gtp[c] : 0.f)) - dot), accumulate);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- focal losses on float targets ---
+// mode 0: focal_loss(normalize=False): mean_i w_i * bce_i, w = pt^gamma detached (loss.py:158-176)
+// mode 1: sigmoid_focal_loss: sum_i alpha_t * bce_i * (1-p_t)^gamma, gradient through the factor (:179-201)
+// mode 2: focal_loss(normalize=True): value sum_i bce_i (the normalisation cancels identically)
+__device__ __forceinline__ void focal_term(float x, float y, float gamma, float alpha, int mode, float& val,
+                                           float& grad) {
+  const float bce = (1.f - y) * x + (softplus_neg_abs(x) + fmaxf(-x, 0.f));
+  const float p = sigmoidf_(x);
+  const float dbce = p - y;
+  if (mode == 2) {
+    val = bce;
+    grad = dbce;
+  } else if (mode == 0) {
+    const float pt = (1.f - p) * y + p * (1.f - y);
+    const float w = powf(pt, gamma);
+    val = w * bce;
+    grad = w * dbce;
+  } else {
+    const float p_t = p * y + (1.f - p) * (1.f - y);
+    const float q = 1.f - p_t;                 // modulating base
+    const float dq = -(2.f * y - 1.f) * p * (1.f - p);  // d(1 - p_t)/dx
+    const float qg = powf(q, gamma);
+    const float dqg = (q > 0.f) ? gamma * powf(q, gamma - 1.f) * dq : 0.f;
+    const float a = alpha >= 0.f ? alpha * y + (1.f - alpha) * (1.f - y) : 1.f;
+    val = a * bce * qg;
+    grad = a * (dbce * qg + bce * dqg);
+  }
+}
+__global__ __launch_bounds__(256) void focal_partial_kernel(const float* __restrict__ logits,
+                                                            const float* __restrict__ target, int64_t n, float gamma,
+                                                            float alpha, int mode, double* __restrict__ stats) {
+  double v[1] = {0.0};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float val, g;
+    focal_term(logits[i], target[i], gamma, alpha, mode, val, g);
+    v[0] += (double)val;
+  }
+  block_sum_store<1>(v, stats + 1 + blockIdx.x);
+}
+__global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict__ logits,
+                                                        const float* __restrict__ target, int64_t n, float gamma,
+                                                        float alpha, int mode, float scale,
+                                                        const float* __restrict__ grad_scale,
+                                                        float* __restrict__ dlogits) {
+  const float k = upstream_scale(grad_scale) * scale;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float val, g;
+    focal_term(logits[i], target[i], gamma, alpha, mode, val, g);
+    dlogits[i] = k * g;
   }
 }
 
@@ -321,26 +380,26 @@ __global__ __launch_bounds__(256) void soft_ce_bwd_kernel(const float* __restric
 
 using namespace evk;
 
+extern "C" int64_t evk_loss_stats_doubles(int32_t K) { return (int64_t)K * (1 + kLossBlocks); }
+extern "C" int64_t evk_prob_stats_doubles(int32_t C) { return (int64_t)3 * C * (1 + kStreamBlocks); }
+
 extern "C" int evk_soft_ce_fwd(const float* logits, const float* target, int64_t npix, int32_t C, float* loss,
                                double* stats, void* stream) {
   EVK_REQUIRE(logits && target && loss && stats && npix > 0 && C >= 1, EVK_E_INVALID, "soft_ce_fwd: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  const int nb = loss_grid(npix);
+  const int nb = fwd_grid(npix, kLossPix, kLossBlocks);
   hipLaunchKernelGGL(soft_ce_partial_kernel, dim3(nb), dim3(256), 0, st, logits, target, npix, C, stats);
   hipLaunchKernelGGL(finalize_partials_kernel, dim3(1), dim3(256), 0, st, stats, 1, nb);
-  hipLaunchKernelGGL(soft_ce_finish_kernel, dim3(1), dim3(64), 0, st, (const double*)stats, 1.0 / (double)npix, loss);
+  hipLaunchKernelGGL(loss_scale_store_kernel, dim3(1), dim3(64), 0, st, (const double*)stats, 1.0 / (double)npix, loss);
   return check_launch("soft_ce_fwd");
 }
 extern "C" int evk_soft_ce_bwd(const float* logits, const float* target, int64_t npix, int32_t C,
                                const float* grad_scale, float* dlogits, void* stream) {
   EVK_REQUIRE(logits && target && dlogits && npix > 0 && C >= 1, EVK_E_INVALID, "soft_ce_bwd: bad argument");
-  const int nb = (int)((npix + 255) / 256 > 4096 ? 4096 : (npix + 255) / 256);
-  hipLaunchKernelGGL(soft_ce_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, logits, target, npix, C,
-                     (float)(1.0 / (double)npix), grad_scale, dlogits);
+  hipLaunchKernelGGL(soft_ce_bwd_kernel, dim3(bwd_grid(npix)), dim3(256), 0, (hipStream_t)stream, logits, target, npix,
+                     C, (float)(1.0 / (double)npix), grad_scale, dlogits);
   return check_launch("soft_ce_bwd");
 }
-
-extern "C" int64_t evk_loss_stats_doubles(int32_t K) { return (int64_t)K * (1 + kLossBlocks); }
 
 extern "C" int evk_bce_fwd_ex(const float* logits, const int64_t* labels, int64_t npix, int64_t ignore_index,
                               float label_smoothing, float pos_weight, int32_t reduction, float* loss, double* stats,
@@ -348,14 +407,14 @@ extern "C" int evk_bce_fwd_ex(const float* logits, const int64_t* labels, int64_
   EVK_REQUIRE(logits && labels && loss && stats && npix > 0, EVK_E_INVALID, "bce_fwd: bad argument");
   EVK_REQUIRE(reduction == 0 || reduction == 1, EVK_E_UNSUPPORTED, "bce_fwd: reduction must be 0 (mean) or 1 (sum)");
   hipStream_t st = (hipStream_t)stream;
-  const int nb = loss_grid(npix);
+  const int nb = fwd_grid(npix, kLossPix, kLossBlocks);
   hipLaunchKernelGGL(bce_partial_kernel, dim3(nb), dim3(256), 0, st, logits, labels, npix, ignore_index,
                      label_smoothing, pos_weight, stats);
   hipLaunchKernelGGL(finalize_partials_kernel, dim3(2), dim3(256), 0, st, stats, 2, nb);
   if (reduction == 0) {
     hipLaunchKernelGGL(mean_loss_kernel, dim3(1), dim3(64), 0, st, (const double*)stats, loss);
   } else {
-    hipLaunchKernelGGL(sum_loss_kernel, dim3(1), dim3(64), 0, st, (const double*)stats, loss);
+    hipLaunchKernelGGL(loss_scale_store_kernel, dim3(1), dim3(64), 0, st, (const double*)stats, 1.0, loss);
   }
   return check_launch("bce_fwd");
 }
@@ -367,9 +426,9 @@ extern "C" int evk_bce_bwd_ex(const float* logits, const int64_t* labels, int64_
                               float label_smoothing, float pos_weight, int32_t reduction, const double* stats,
                               const float* grad_scale, float* dlogits, int32_t accumulate, void* stream) {
   EVK_REQUIRE(logits && labels && stats && dlogits && npix > 0, EVK_E_INVALID, "bce_bwd: bad argument");
-  hipLaunchKernelGGL(bce_bwd_kernel, dim3((int)((npix + 255) / 256 > 4096 ? 4096 : (npix + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, logits, labels, npix, ignore_index, label_smoothing, pos_weight,
-                     reduction == 1 ? 1 : 0, stats, grad_scale, dlogits, accumulate);
+  hipLaunchKernelGGL(bce_bwd_kernel, dim3(bwd_grid(npix)), dim3(256), 0, (hipStream_t)stream, logits, labels, npix,
+                     ignore_index, label_smoothing, pos_weight, reduction == 1 ? 1 : 0, stats, grad_scale, dlogits,
+                     accumulate);
   return check_launch("bce_bwd");
 }
 extern "C" int evk_bce_bwd(const float* logits, const int64_t* labels, int64_t npix, int64_t ignore_index,
@@ -386,7 +445,7 @@ extern "C" int evk_dice_stats(const float* logits, const int64_t* labels, int64_
               "dice_stats: C=%d outside [1,%d] (the softmax path keeps 256 x 2C doubles in 64 KiB of LDS)", C,
               kDiceMaxClasses);
   hipStream_t st = (hipStream_t)stream;
-  const int nb = loss_grid(npix);
+  const int nb = fwd_grid(npix, kLossPix, kLossBlocks);
   if (C == 1) {
     hipLaunchKernelGGL(dice_partial_kernel<1>, dim3(nb), dim3(256), 0, st, logits, labels, npix, C, ignore_index, stats);
   } else {
@@ -409,7 +468,7 @@ extern "C" int evk_dice_bwd(const float* logits, const int64_t* labels, int64_t 
                             float* dlogits, int32_t accumulate, void* stream) {
   EVK_REQUIRE(logits && labels && stats && dlogits && npix > 0 && C >= 1 && C <= kMaxClasses, EVK_E_INVALID,
               "dice_bwd: bad argument");
-  const int nb = (int)((npix + 255) / 256 > 4096 ? 4096 : (npix + 255) / 256);
+  const int nb = bwd_grid(npix);
   if (C == 1)
     hipLaunchKernelGGL(dice_bwd_kernel<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, logits, labels, npix, C,
                        ignore_index, stats, smooth, ignore_channel, grad_scale, dlogits, accumulate);
@@ -423,7 +482,7 @@ extern "C" int evk_ce_fwd(const float* logits, const int64_t* labels, int64_t np
                           float label_smoothing, float* loss, double* stats, void* stream) {
   EVK_REQUIRE(logits && labels && loss && stats && npix > 0 && C >= 1, EVK_E_INVALID, "ce_fwd: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  const int nb = loss_grid(npix);
+  const int nb = fwd_grid(npix, kLossPix, kLossBlocks);
   hipLaunchKernelGGL(ce_partial_kernel, dim3(nb), dim3(256), 0, st, logits, labels, npix, C, ignore_index, stats);
   hipLaunchKernelGGL(finalize_partials_kernel, dim3(3), dim3(256), 0, st, stats, 3, nb);
   hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, st, (const double*)stats, C, label_smoothing, loss);
@@ -433,8 +492,48 @@ extern "C" int evk_ce_bwd(const float* logits, const int64_t* labels, int64_t np
                           float label_smoothing, const double* stats, const float* grad_scale, float* dlogits,
                           int32_t accumulate, void* stream) {
   EVK_REQUIRE(logits && labels && stats && dlogits && npix > 0 && C >= 1, EVK_E_INVALID, "ce_bwd: bad argument");
-  const int nb = (int)((npix + 255) / 256 > 4096 ? 4096 : (npix + 255) / 256);
-  hipLaunchKernelGGL(ce_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, logits, labels, npix, C, ignore_index,
-                     label_smoothing, stats, grad_scale, dlogits, accumulate);
+  hipLaunchKernelGGL(ce_bwd_kernel, dim3(bwd_grid(npix)), dim3(256), 0, (hipStream_t)stream, logits, labels, npix, C,
+                     ignore_index, label_smoothing, stats, grad_scale, dlogits, accumulate);
   return check_launch("ce_bwd");
+}
+
+extern "C" int evk_prob_stats(const float* logits, const int64_t* labels, int64_t npix, int32_t C, int64_t ignore_index,
+                              double* stats, void* stream) {
+  EVK_REQUIRE(logits && labels && stats, EVK_E_INVALID, "prob_stats: null pointer");
+  EVK_REQUIRE(C >= 1 && C <= kProbStatsMaxC, EVK_E_UNSUPPORTED, "prob_stats: C=%d outside [1,%d]", C, kProbStatsMaxC);
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = fwd_grid(npix, kStreamPix, kStreamBlocks);
+  hipLaunchKernelGGL(prob_stats_kernel, dim3(nblk), dim3(256), 0, st, logits, labels, npix, C, ignore_index, stats);
+  hipLaunchKernelGGL(finalize_partials_in_order_kernel, dim3(1), dim3(256), 0, st, stats, 3 * C, nblk);
+  return check_launch("prob_stats");
+}
+extern "C" int evk_prob_stats_bwd(const float* logits, const int64_t* labels, int64_t npix, int32_t C,
+                                  int64_t ignore_index, const float* g_tp, const float* g_sp, float* dlogits,
+                                  int32_t accumulate, void* stream) {
+  EVK_REQUIRE(logits && labels && g_tp && g_sp && dlogits, EVK_E_INVALID, "prob_stats_bwd: null pointer");
+  EVK_REQUIRE(C >= 1 && C <= kProbStatsMaxC, EVK_E_UNSUPPORTED, "prob_stats_bwd: C=%d outside [1,%d]", C,
+              kProbStatsMaxC);
+  hipLaunchKernelGGL(prob_stats_bwd_kernel, dim3(bwd_grid(npix)), dim3(256), 0, (hipStream_t)stream, logits, labels,
+                     npix, C, ignore_index, g_tp, g_sp, dlogits, accumulate);
+  return check_launch("prob_stats_bwd");
+}
+
+extern "C" int evk_focal_fwd(const float* logits, const float* target, int64_t n, float gamma, float alpha,
+                             int32_t mode, int32_t mean, float* loss, double* stats, void* stream) {
+  EVK_REQUIRE(logits && target && loss && stats, EVK_E_INVALID, "focal_fwd: null pointer");
+  EVK_REQUIRE(mode >= 0 && mode <= 2, EVK_E_INVALID, "focal_fwd: mode %d", mode);
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = fwd_grid(n, kStreamPix, kStreamBlocks);
+  hipLaunchKernelGGL(focal_partial_kernel, dim3(nblk), dim3(256), 0, st, logits, target, n, gamma, alpha, mode, stats);
+  hipLaunchKernelGGL(finalize_partials_in_order_kernel, dim3(1), dim3(64), 0, st, stats, 1, nblk);
+  hipLaunchKernelGGL(loss_scale_store_kernel, dim3(1), dim3(64), 0, st, (const double*)stats,
+                     mean ? 1.0 / (double)n : 1.0, loss);
+  return check_launch("focal_fwd");
+}
+extern "C" int evk_focal_bwd(const float* logits, const float* target, int64_t n, float gamma, float alpha,
+                             int32_t mode, int32_t mean, const float* grad_scale, float* dlogits, void* stream) {
+  EVK_REQUIRE(logits && target && dlogits, EVK_E_INVALID, "focal_bwd: null pointer");
+  hipLaunchKernelGGL(focal_bwd_kernel, dim3(bwd_grid(n)), dim3(256), 0, (hipStream_t)stream, logits, target, n, gamma,
+                     alpha, mode, mean ? 1.f / (float)n : 1.f, grad_scale, dlogits);
+  return check_launch("focal_bwd");
 }

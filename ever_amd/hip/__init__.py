@@ -35,11 +35,12 @@ def compiler_opaque(model=None):
     import types
     from . import functional_next
     disable = torch.compiler.disable
-    for mod in (functional, functional_next):
+    # functional_next re-exports the per-pixel cross entropy and OHEM, which live in losses.py
+    for mod, homes in ((functional, ()), (functional_next, ('ever_amd.hip.losses',))):
         for name, obj in list(vars(mod).items()):
             if name.startswith('_') or not isinstance(obj, types.FunctionType):
                 continue
-            if getattr(obj, '__module__', None) not in (mod.__name__, 'ever_amd.hip.oplib'):
+            if getattr(obj, '__module__', None) not in (mod.__name__, 'ever_amd.hip.oplib') + homes:
                 continue
             setattr(mod, name, disable(obj, recursive=True))
     _OPAQUE[0] = True

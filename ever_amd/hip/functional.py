@@ -10,7 +10,7 @@ The wrappers live in one module per kernel family (round 6: this file used to ho
   conv.py        convolution forward / data gradient / weight gradient, fork nodes, gradient slots, transposed, stem
   norm.py        BatchNorm (+ residual, ReLU), the stem's BatchNorm + ReLU + max-pool
   pointwise.py   ReLU, add, pools, resampling, global average pool, FS-Relation, BatchNorm + ReLU + classifier dot, mean
-  losses.py      BCE / dice / CE / soft-CE / tversky / focal / confusion matrix
+  losses.py      BCE / dice / CE / soft-CE / tversky / focal / per-pixel CE / OHEM / confusion matrix
   depthwise.py   depthwise convolution (groups == channels), the broadcast of a 1x1 map
   hr.py          HRNet: the multi-resolution exchange as one node, bilinear up-sampling into a concat buffer
   fuse.py        BiFPN: the learned weighted fusion node, nearest x2 as an index shift

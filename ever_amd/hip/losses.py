@@ -1,5 +1,5 @@
 """Pixel losses and metrics of the host wrappers (reference ever/module/loss.py:10-75,207-235 and the FarSeg++ / ChangeStar
-losses; include/ever_hip.h: evk_bce_* / evk_dice_* / evk_ce_* / evk_focal_* / evk_confusion_*).  Part of the
+losses; include/ever_hip.h: evk_bce_* / evk_dice_* / evk_ce_* / evk_focal_* / evk_ohem_* / evk_confusion_*).  Part of the
 hip/functional.py facade."""
 import ctypes
 import os
@@ -12,7 +12,7 @@ from .. import _C
 from . import timing, weight_planes
 from .workspace import workspace
 from ._base import (  # noqa: F401
-    _require_cuda, _stream, _timed_call, as_nhwc, is_nhwc,
+    _require_cuda, _stream, _timed_call, as_nhwc, is_nhwc, HipPathError,
 )
 
 
@@ -29,6 +29,12 @@ def _labels(y_true, npix, what):
     if y_true.numel() != npix:
         raise ValueError(f'{what}: labels have {y_true.numel()} elements, logits have {npix} pixels')
     return y_true
+
+
+def _backward_buffers(g, like):
+    """What every backward here starts with: the upstream gradient as contiguous fp32, and a fresh gradient buffer laid out
+    like the forward's input."""
+    return g.contiguous().float(), torch.empty_like(like)
 
 
 class _BceFn(Function):
@@ -49,8 +55,7 @@ class _BceFn(Function):
     @once_differentiable
     def backward(ctx, g):
         logits, labels, stats = ctx.saved_tensors
-        g = g.contiguous().float()
-        d = torch.empty_like(logits)
+        g, d = _backward_buffers(g, logits)
         _timed_call('resample_loss', 16.0 * logits.numel(), 'evk_bce_bwd_ex', logits.data_ptr(), labels.data_ptr(), logits.numel(), ctx.ignore_index, ctx.eps,
                     ctx.pw, ctx.red, stats.data_ptr(), g.data_ptr(), d.data_ptr(), 0, _stream())
         return d, None, None, None, None, None
@@ -83,16 +88,15 @@ def bce_with_logits(y_pred, y_true, ignore_index=255, label_smoothing=0.0, pos_w
         # loss.py:10-17,229-235): a data-dependent shape, so the compaction is a boolean index (one host round trip, as in the
         # reference).  Per pixel BCE(z, t) = t * CE([0, z], 1) + (1 - t) * CE([0, z], 0): the two-class per-pixel cross entropy
         # kernel on the logit pair (0, z), which is the same softplus arithmetic.
-        from . import functional_next as HN
         z = y_pred.reshape(-1, 1, 1, 1)
         z2 = as_nhwc(torch.cat([torch.zeros_like(z), z], dim=1), 'bce.none')
         yl = labels.reshape(-1, 1, 1)
         valid = yl != ignore_index
         if not label_smoothing and pw == 1.0:
-            per = HN.cross_entropy_per_pixel(z2, yl, ignore_index)
+            per = cross_entropy_per_pixel(z2, yl, ignore_index)
         else:
-            l1 = HN.cross_entropy_per_pixel(z2, torch.where(valid, torch.ones_like(yl), yl), ignore_index)
-            l0 = HN.cross_entropy_per_pixel(z2, torch.where(valid, torch.zeros_like(yl), yl), ignore_index)
+            l1 = cross_entropy_per_pixel(z2, torch.where(valid, torch.ones_like(yl), yl), ignore_index)
+            l0 = cross_entropy_per_pixel(z2, torch.where(valid, torch.zeros_like(yl), yl), ignore_index)
             t = yl.to(torch.float32)
             if label_smoothing:
                 t = torch.where(yl == 0, t + label_smoothing, t - label_smoothing)
@@ -139,12 +143,11 @@ class _DiceFn(Function):
         logits, labels, stats = ctx.saved_tensors
         smooth, ignore_index, ignore_channel, world = ctx.cfg
         n, c, h, w = logits.shape
-        g = g.contiguous().float()
+        g, d = _backward_buffers(g, logits)
         if world > 1:
             # backward of torch.distributed.nn.all_reduce(SUM) is an all_reduce(SUM) of the upstream grads
             g = g.clone()
             _sum_over_ranks(g, 'dice_grad')
-        d = torch.empty_like(logits)
         _timed_call('resample_loss', (8.0 * c + 8.0) * n * h * w, 'evk_dice_bwd', logits.data_ptr(), labels.data_ptr(), n * h * w, c, ignore_index, stats.data_ptr(),
                 smooth, ignore_channel, g.data_ptr(), d.data_ptr(), 0, _stream())
         return d, None, None, None, None, None
@@ -181,8 +184,7 @@ class _CeFn(Function):
         logits, labels, stats = ctx.saved_tensors
         ignore_index, eps = ctx.cfg
         n, c, h, w = logits.shape
-        g = g.contiguous().float()
-        d = torch.empty_like(logits)
+        g, d = _backward_buffers(g, logits)
         _C.call('evk_ce_bwd', logits.data_ptr(), labels.data_ptr(), n * h * w, c, ignore_index, eps, stats.data_ptr(),
                 g.data_ptr(), d.data_ptr(), 0, _stream())
         return d, None, None, None
@@ -204,8 +206,7 @@ class _SoftCeFn(Function):
     def backward(ctx, g):
         logits, target = ctx.saved_tensors
         n, c, h, w = logits.shape
-        g = g.contiguous().float()
-        d = torch.empty_like(logits)
+        g, d = _backward_buffers(g, logits)
         _C.call('evk_soft_ce_bwd', logits.data_ptr(), target.data_ptr(), n * h * w, c, g.data_ptr(), d.data_ptr(),
                 _stream())
         return d, None
@@ -234,15 +235,14 @@ def cross_entropy(y_pred, y_true, ignore_index=255, label_smoothing=0.0, reducti
         y_pred = y_pred.reshape(y_pred.shape[0], y_pred.shape[1], 1, 1)
     y_pred = as_nhwc(y_pred, 'cross_entropy')
     if reduction == 'none':
-        from . import functional_next as HN
         n, c, h, w = y_pred.shape
         yt = y_true.to(torch.int64).reshape(n, h, w)
-        out = HN.cross_entropy_per_pixel(y_pred, yt, ignore_index)
+        out = cross_entropy_per_pixel(y_pred, yt, ignore_index)
         if label_smoothing:
             valid = yt != ignore_index
             uni = None
             for k in range(c):
-                t = HN.cross_entropy_per_pixel(y_pred, torch.where(valid, torch.full_like(yt, k), yt), ignore_index)
+                t = cross_entropy_per_pixel(y_pred, torch.where(valid, torch.full_like(yt, k), yt), ignore_index)
                 uni = t if uni is None else uni + t
             out = out * (1.0 - label_smoothing) + uni * (label_smoothing / c)
         return out.reshape(y_true.shape)
@@ -253,7 +253,7 @@ def cross_entropy(y_pred, y_true, ignore_index=255, label_smoothing=0.0, reducti
     return torch.where(count > 0, mean * count, torch.zeros_like(mean))
 
 
-# ------------------------------------------------------------------ SURVEY §8 f2 / f3 rows
+# ------------------------------------------------------------------ class-probability statistics, tversky, focal
 class _ProbStatsFn(Function):
     """(tp, sum_p, sum_y) per class over the valid pixels as a float32 [3, C] tensor; backward is the adjoint
     kernel, so any differentiable function of the statistics (tversky, dice variants) trains through it."""
@@ -274,8 +274,7 @@ class _ProbStatsFn(Function):
     def backward(ctx, g):
         logits, labels = ctx.saved_tensors
         n, c, h, w = logits.shape
-        g = g.float().contiguous()
-        d = torch.empty_like(logits)
+        g, d = _backward_buffers(g, logits)
         _C.call('evk_prob_stats_bwd', logits.data_ptr(), labels.data_ptr(), n * h * w, c, ctx.ignore_index,
                 g[0].data_ptr(), g[1].data_ptr(), d.data_ptr(), 0, _stream())
         return d, None, None
@@ -335,8 +334,7 @@ class _FocalFn(Function):
     def backward(ctx, g):
         logits, target = ctx.saved_tensors
         gamma, alpha, mode, mean = ctx.cfg
-        g = g.contiguous().float()
-        d = torch.empty_like(logits)
+        g, d = _backward_buffers(g, logits)
         _C.call('evk_focal_bwd', logits.data_ptr(), target.data_ptr(), logits.numel(), gamma, alpha, mode, mean,
                 g.data_ptr(), d.data_ptr(), _stream())
         return d, None, None, None, None, None
@@ -364,6 +362,72 @@ def sigmoid_focal_loss(y_pred, y_true, alpha=-1, gamma=2, reduction='mean'):
     if reduction not in ('mean', 'sum'):
         raise NotImplementedError("sigmoid_focal_loss: reduction must be 'mean' or 'sum' on the HIP path")
     return _focal(y_pred, y_true, gamma, alpha, 1, 1 if reduction == 'mean' else 0, 'sigmoid_focal_loss')
+
+
+# ------------------------------------------------------------------ per-pixel cross entropy, OHEM
+class _CePixelFn(Function):
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index):
+        n, c, h, w = logits.shape
+        out = torch.empty((n, h, w), device=logits.device, dtype=torch.float32)
+        _C.call('evk_ce_pixel_fwd', logits.data_ptr(), labels.data_ptr(), n * h * w, c, ignore_index, out.data_ptr(),
+                _stream())
+        ctx.save_for_backward(logits, labels)
+        ctx.ignore_index = ignore_index
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        logits, labels = ctx.saved_tensors
+        n, c, h, w = logits.shape
+        g, d = _backward_buffers(g, logits)
+        _C.call('evk_ce_pixel_bwd', logits.data_ptr(), labels.data_ptr(), n * h * w, c, ctx.ignore_index, g.data_ptr(),
+                d.data_ptr(), _stream())
+        return d, None, None
+
+
+def cross_entropy_per_pixel(y_pred, y_true, ignore_index=255):
+    """F.cross_entropy(y_pred, y_true, ignore_index=..., reduction='none') -> [N, H, W]"""
+    _require_cuda(y_pred, 'cross_entropy_per_pixel')
+    y_pred = as_nhwc(y_pred, 'cross_entropy_per_pixel')
+    if y_pred.shape[1] < 2:
+        raise HipPathError('cross_entropy_per_pixel: needs at least 2 classes')
+    yt = y_true.to(torch.int64).contiguous()
+    if yt.numel() != y_pred.numel() // y_pred.shape[1]:
+        raise ValueError('cross_entropy_per_pixel: label / logit pixel counts differ')
+    return _CePixelFn.apply(y_pred, yt, int(ignore_index))
+
+
+class _OhemFn(Function):
+    @staticmethod
+    def forward(ctx, losses, keep):
+        lib = _C.load()
+        state = torch.empty((lib.evk_ohem_state_bytes(),), device=losses.device, dtype=torch.uint8)
+        loss = torch.empty((), device=losses.device, dtype=torch.float32)
+        _C.call('evk_ohem_fwd', losses.data_ptr(), losses.numel(), keep, loss.data_ptr(), state.data_ptr(), _stream())
+        ctx.save_for_backward(losses, state)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        losses, state = ctx.saved_tensors
+        g, d = _backward_buffers(g, losses)
+        _C.call('evk_ohem_bwd', losses.data_ptr(), losses.numel(), state.data_ptr(), g.data_ptr(), d.data_ptr(), _stream())
+        return d, None
+
+
+def online_hard_example_mining(losses, keep_ratio):
+    """reference ever/module/loss.py:146-155: mean of the non-zero values among the int(keep_ratio * N) largest."""
+    assert 0 < keep_ratio < 1, 'The value of keep_ratio must be from 0 to 1.'
+    if not losses.is_cuda or losses.dtype != torch.float32:
+        raise HipPathError('online_hard_example_mining: fp32 CUDA tensor required')
+    flat = losses.contiguous().view(-1) if losses.is_contiguous() else losses.reshape(-1).contiguous()
+    keep = int(keep_ratio * flat.numel())
+    if keep < 1:
+        raise ValueError('online_hard_example_mining: keep_ratio * numel < 1')
+    return _OhemFn.apply(flat, keep)
 
 
 def confusion_matrix_update(cm, y_true, y_pred=None, logits=None):

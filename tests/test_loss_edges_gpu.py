@@ -1,4 +1,4 @@
-"""The pixel losses and evaluation metrics (csrc/loss.hip and the loss / metric half of csrc/next_rows.hip) at the edges
+"""The pixel losses and evaluation metrics (csrc/loss.hip, csrc/loss_pixel.hip and csrc/metric.hip) at the edges
 of their launch grids, class counts and labels.
 
 Reference: the same formula in float64 torch on the CPU, from the same fp32 inputs; gradients by autograd on it.
@@ -7,9 +7,10 @@ maximum with atol = 0 — at 4 million pixels a gradient is 2.5e-7, so any absol
 an integer (valid-pixel counts, label histograms, confusion matrices, numbers of kept elements) is compared exactly.
 
 Grid facts the sizes below are chosen around:
-  loss.hip forward     ceil(npix / 2048) workgroups, at most 2048: second workgroup at 2,049 pixels, cap at 4,194,304
+  BCE/dice/CE forward  ceil(npix / 2048) workgroups, at most 2048: second workgroup at 2,049 pixels, cap at 4,194,304
   every backward       ceil(n / 256) workgroups, at most 4096: cap at 1,048,576 elements
-  next_rows.hip        ceil(n / 1024) workgroups, at most 256: cap at 262,144 elements
+  statistics, focal,   ceil(n / 1024) workgroups, at most 256: cap at 262,144 elements
+  OHEM, confusion
 Logits are laid out [1, C, H, W] over dense NHWC memory, so no transposition kernel runs in front of the loss."""
 import functools
 

@@ -16,7 +16,7 @@ CONV_WGRAD_AUX = ('splitk_reduce', 'colsum_', 'pack_f16x2', 'pack_planar')
 BN = ('bn_',)
 # the memory-bound kernels north_star names, as bench.py's `resample_loss` spans bracket them (hip/functional.py: the
 # bilinear forward / backward and the bce / dice / ce calls with their tiny finalisation kernels)
-RESAMPLE_LOSS = ('^bilinear_', '^mean_loss', '^finalize_partials', '^bce_', '^dice_', '^ce_', '^focal_', '^prob_stats', '^ohem_', '^soft_ce_', '^sum_loss', '^nr_finalize')   # '^' = the bare name starts with it
+RESAMPLE_LOSS = ('^bilinear_', '^mean_loss', '^finalize_partials', '^bce_', '^dice_', '^ce_', '^focal_', '^prob_stats', '^ohem_', '^soft_ce_', '^loss_scale_store')   # '^' = the bare name starts with it
 
 FAMILIES = (
     ('conv_igemm', 'conv_igemm (forward + data gradient: conv3x3_* (wino, halo) / conv1x1_* (dma, ps2, sp, smallm) / conv_igemm_x3ws / '
@@ -29,7 +29,7 @@ FAMILIES = (
     ('pointwise', 'other streaming kernels of the model (relation_* / nearest2x_* / gap_* / mean4 / ew / stem_s2d / maxpool / gn_* / concat / '
                   'channel_scale / confusion / subsample2 / hr_fuse_* / d4_* / wfuse_* / augment_*)', ('^relation_', '^nearest2x_', '^gap_', '^mean4', '^ew_', '^stem_s2d_kernel', '^maxpool', '^gn_', '^concat2',
                                                 '^split2', '^channel_scale', '^confusion', '^nchw_', '^nhwc_', '^bias_rows', '^pad_channels', '^unpad_channels',
-                                                '^relu_bits_apply', '^scale_store', '^subsample2', '^broadcast_hw', '^sum_hw', '^hr_fuse_', '^d4_', '^wfuse_', '^augment_')),
+                                                '^relu_bits_apply', '^subsample2', '^broadcast_hw', '^sum_hw', '^hr_fuse_', '^d4_', '^wfuse_', '^augment_')),
     ('depthwise', 'depthwise convolution (depthwise_fwd / depthwise_bwd / depthwise_reduce kernels: exact fp32 on the vector ALUs)',
      ('^depthwise_',)),
     ('ln', 'row LayerNorm and layer-scale residual (ln_fwd / ln_bwd / ln_records_finalize, lscale_fwd / lscale_bwd kernels)',
