@@ -203,6 +203,7 @@ SIGNATURES = {
     'evk_ohem_bwd': (c_int, [P, c_i64, P, P, P, P]),
     'evk_depthwise_fwd': (c_int, [_DP, P, P, P, P, c_u32, P]),
     'evk_depthwise_bwd_workspace_bytes': (c_size_t, [_DP]),
+    'evk_depthwise_plan': (c_int, [_DP, C.POINTER(c_i32)]),
     'evk_depthwise_bwd': (c_int, [_DP, P, P, P, P, P, P, P, P, c_size_t, P]),
     'evk_broadcast_hw': (c_int, [P, P, c_i32, c_i64, c_i32, P]),
     'evk_sum_hw': (c_int, [P, P, c_i32, c_i64, c_i32, P]),

@@ -370,6 +370,12 @@ int check_desc(const evk_conv_desc* d, const char* what) {
               "%s: stride (%d, %d) must be 1 or 2", what, d->stride_h, d->stride_w);
   EVK_REQUIRE(d->dil_h >= 1 && d->dil_w >= 1 && d->pad_h >= 0 && d->pad_w >= 0, EVK_E_UNSUPPORTED,
               "%s: dilation must be positive and padding non-negative", what);
+  EVK_REQUIRE(d->H + 2 * (int64_t)d->pad_h >= (int64_t)d->dil_h * (d->kh - 1) + 1, EVK_E_INVALID,
+              "%s: kernel extent %lld along H exceeds the padded input (%lld): H + 2 * pad_h < dil_h * (kh - 1) + 1", what,
+              (long long)d->dil_h * (d->kh - 1) + 1, (long long)d->H + 2 * (long long)d->pad_h);
+  EVK_REQUIRE(d->W + 2 * (int64_t)d->pad_w >= (int64_t)d->dil_w * (d->kw - 1) + 1, EVK_E_INVALID,
+              "%s: kernel extent %lld along W exceeds the padded input (%lld): W + 2 * pad_w < dil_w * (kw - 1) + 1", what,
+              (long long)d->dil_w * (d->kw - 1) + 1, (long long)d->W + 2 * (long long)d->pad_w);
   EVK_REQUIRE(d->Ho == (d->H + 2 * d->pad_h - d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1 &&
                   d->Wo == (d->W + 2 * d->pad_w - d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1,
               EVK_E_INVALID, "%s: output size (%d, %d) does not follow from the geometry", what, d->Ho, d->Wo);
@@ -384,24 +390,53 @@ DwArgs make_args(const evk_conv_desc* d) {
   return a;
 }
 
-// backward tiling: channel lanes (a power of two <= 64), strips per workgroup, tile counts
-void bwd_plan(DwArgs& a) {
+// The forms and tilings of a descriptor in scope: the one place the launchers, the workspace size and evk_depthwise_plan
+// take them from.
+struct DwPlan {
+  int fkw, fsw, fd1;          // forward instantiation <KW, SW, D1>
+  int fstrips;                // forward: strips of kTW output pixels per row
+  int64_t fblocks;            // forward: workgroups
+  int bkw, bs1d1;             // backward instantiation <KW, S1D1>
+  int cl, ps;                 // backward: channel lanes (a power of two <= 64) and strips per workgroup
+  int bstrips, strip_groups, row_tiles, cblocks;
+  int64_t tiles;
+};
+
+DwPlan dw_plan(const DwArgs& a) {
+  DwPlan p;
   const int C4 = a.C / 4;
+  p.fkw = a.kw; p.fsw = a.sw; p.fd1 = a.dw == 1 ? 1 : 0;
+  p.fstrips = ceil_div(a.Wo, kTW);
+  p.fblocks = ((int64_t)a.N * a.Ho * p.fstrips * C4 + 255) / 256;
+  p.bkw = a.kw; p.bs1d1 = (a.sw == 1 && a.dw == 1) ? 1 : 0;
   int cl = 1;
   while (cl < C4 && cl < 16) cl *= 2;
   // the widest of 16 / 32 / 64 lanes that idles no more of them than a narrower one (C = 304: 16 lanes x 5 blocks)
   for (int w = 32; w <= 64 && C4 > 16; w *= 2)
     if ((int64_t)ceil_div(C4, w) * w <= (int64_t)ceil_div(C4, cl) * cl) cl = w;
-  a.cl = cl;
-  a.ps = 256 / cl;
+  p.cl = cl;
+  p.ps = 256 / cl;
   const int wmax = a.W > a.Wo ? a.W : a.Wo;
   const int hmax = a.H > a.Ho ? a.H : a.Ho;
-  a.strips = ceil_div(wmax, kTB);
-  a.strip_groups = ceil_div(a.strips, a.ps);
-  a.row_tiles = ceil_div(hmax, kTH);
+  p.bstrips = ceil_div(wmax, kTB);
+  p.strip_groups = ceil_div(p.bstrips, p.ps);
+  p.row_tiles = ceil_div(hmax, kTH);
+  p.cblocks = ceil_div(C4, cl);
+  p.tiles = (int64_t)a.N * p.row_tiles * p.strip_groups;
+  return p;
 }
 
-int64_t bwd_tiles(const DwArgs& a) { return (int64_t)a.N * a.row_tiles * a.strip_groups; }
+bool fwd_fits(const DwPlan& p) { return p.fblocks < 0x7fffffff; }
+bool bwd_fits(const DwPlan& p) { return p.tiles < 0x7fffffff && p.cblocks <= 65535; }
+
+void set_bwd_tiling(DwArgs& a, const DwPlan& p) {
+  a.cl = p.cl; a.ps = p.ps;
+  a.strips = p.bstrips; a.strip_groups = p.strip_groups; a.row_tiles = p.row_tiles;
+}
+
+size_t slab_bytes(const DwArgs& a, const DwPlan& p) {
+  return (size_t)p.tiles * (size_t)(a.kh * a.kw + 1) * (size_t)a.C * sizeof(float);
+}
 
 }  // namespace
 
@@ -417,18 +452,31 @@ extern "C" int evk_depthwise_fwd(const evk_conv_desc* d, const float* x, const f
   DwArgs a = make_args(d);
   a.x = x; a.w = w; a.bias = bias; a.out = y;
   a.relu = (flags & EVK_CONV_RELU) ? 1 : 0;
-  a.strips = ceil_div(a.Wo, kTW);
-  const int64_t blocks = ((int64_t)a.N * a.Ho * a.strips * (a.C / 4) + 255) / 256;
-  EVK_REQUIRE(blocks < 0x7fffffff, EVK_E_UNSUPPORTED, "depthwise_fwd: grid too large");
-  kFwd[a.kw - 1][a.sw - 1][a.dw == 1 ? 1 : 0](a, dim3((unsigned)blocks), (hipStream_t)stream);
+  const DwPlan p = dw_plan(a);
+  EVK_REQUIRE(fwd_fits(p), EVK_E_UNSUPPORTED, "depthwise_fwd: grid too large");
+  a.strips = p.fstrips;
+  kFwd[p.fkw - 1][p.fsw - 1][p.fd1](a, dim3((unsigned)p.fblocks), (hipStream_t)stream);
   return check_launch("depthwise_fwd");
 }
 
 extern "C" size_t evk_depthwise_bwd_workspace_bytes(const evk_conv_desc* d) {
   if (check_desc(d, "depthwise_bwd_workspace_bytes")) return 0;
-  DwArgs a = make_args(d);
-  bwd_plan(a);
-  return (size_t)bwd_tiles(a) * (size_t)(a.kh * a.kw + 1) * (size_t)a.C * sizeof(float);
+  const DwArgs a = make_args(d);
+  return slab_bytes(a, dw_plan(a));
+}
+
+// Host only (no launch): out = {forward KW, SW, D1, forward strips per row, forward workgroups, backward KW, S1D1, channel
+// lanes cl, strips per workgroup ps, backward strips per row, strip groups, row tiles, channel blocks, tiles}
+extern "C" int evk_depthwise_plan(const evk_conv_desc* d, int32_t* out) {
+  int rc = check_desc(d, "depthwise_plan");
+  if (rc) return rc;
+  EVK_REQUIRE(out, EVK_E_INVALID, "depthwise_plan: null pointer");
+  const DwPlan p = dw_plan(make_args(d));
+  EVK_REQUIRE(fwd_fits(p) && bwd_fits(p), EVK_E_UNSUPPORTED, "depthwise_plan: grid too large");
+  const int32_t v[14] = {p.fkw, p.fsw, p.fd1, p.fstrips, (int32_t)p.fblocks, p.bkw, p.bs1d1, p.cl, p.ps, p.bstrips,
+                         p.strip_groups, p.row_tiles, p.cblocks, (int32_t)p.tiles};
+  for (int i = 0; i < 14; ++i) out[i] = v[i];
+  return EVK_OK;
 }
 
 extern "C" int evk_depthwise_bwd(const evk_conv_desc* d, const float* dy, const float* x, const float* y, const float* w,
@@ -439,18 +487,18 @@ extern "C" int evk_depthwise_bwd(const evk_conv_desc* d, const float* dy, const 
   EVK_REQUIRE(!(dw || db) || x, EVK_E_INVALID, "depthwise_bwd: the weight / bias gradient needs x");
   if (!dx && !dw && !db) return EVK_OK;
   DwArgs a = make_args(d);
-  bwd_plan(a);
-  const int64_t tiles = bwd_tiles(a);
+  const DwPlan p = dw_plan(a);
+  set_bwd_tiling(a, p);
+  const int64_t tiles = p.tiles;
   const bool params = dw || db;
   if (params)
-    EVK_REQUIRE(workspace && workspace_bytes >= evk_depthwise_bwd_workspace_bytes(d), EVK_E_WORKSPACE,
-                "depthwise_bwd: workspace of %zu bytes, %zu needed", workspace_bytes, evk_depthwise_bwd_workspace_bytes(d));
-  EVK_REQUIRE(tiles < 0x7fffffff, EVK_E_UNSUPPORTED, "depthwise_bwd: grid too large");
+    EVK_REQUIRE(workspace && workspace_bytes >= slab_bytes(a, p), EVK_E_WORKSPACE,
+                "depthwise_bwd: workspace of %zu bytes, %zu needed", workspace_bytes, slab_bytes(a, p));
+  EVK_REQUIRE(bwd_fits(p), EVK_E_UNSUPPORTED, "depthwise_bwd: grid too large");
   a.dy = dy; a.x = x; a.y = y; a.w = w; a.out = dx;
   a.slab = params ? reinterpret_cast<float*>(workspace) : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  const bool s1d1 = a.sw == 1 && a.dw == 1;
-  kBwd[a.kw - 1][s1d1 ? 1 : 0](a, dim3((unsigned)tiles, (unsigned)ceil_div(a.C / 4, a.cl)), st);
+  kBwd[p.bkw - 1][p.bs1d1](a, dim3((unsigned)tiles, (unsigned)p.cblocks), st);
   if (params) {
     const int taps = a.kh * a.kw;
     hipLaunchKernelGGL(depthwise_reduce_kernel, dim3((unsigned)ceil_div((int64_t)(taps + 1) * (a.C / 4), 4)), dim3(256), 0,

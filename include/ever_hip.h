@@ -871,6 +871,14 @@ int evk_depthwise_fwd(const evk_conv_desc* d, const float* x, const float* w, co
                       uint32_t flags, void* stream);
 /* Host only: bytes of the per-tile weight / bias gradient records of evk_depthwise_bwd (0 for a descriptor out of scope). */
 size_t evk_depthwise_bwd_workspace_bytes(const evk_conv_desc* d);
+/* Host only (no launch): the kernel forms and tilings evk_depthwise_fwd / _bwd and the workspace size take for a descriptor,
+ * from the function they take them from.  out = {forward <KW, SW, D1> (3), forward strips of 8 output pixels per row,
+ * forward workgroups, backward <KW, S1D1> (2), channel lanes cl (a power of two <= 64, of 4 channels each), strips of 4
+ * pixels per workgroup ps (cl * ps == 256), backward strips per row (over max(W, Wo)), strip groups, row tiles (4 rows, over
+ * max(H, Ho)), channel blocks, tiles = N * row tiles * strip groups}; workspace bytes = tiles * (kh * kw + 1) * C * 4.
+ * It refuses what the launches refuse, and a workgroup, tile or channel-block count that does not fit the grid; `out` is
+ * untouched then. */
+int evk_depthwise_plan(const evk_conv_desc* d, int32_t* out /*[14]*/);
 /* Gradients of evk_depthwise_fwd: dx (may be NULL), dw [C][kh][kw] and db [C] (either may be NULL; then x may be NULL
  * too).  y: the forward's output when it fused the ReLU (the mask), else NULL.  One pass over dy and x writes dx and a
  * record of dw / db partial sums per tile; a second kernel sums the records in a fixed order (no atomics). */

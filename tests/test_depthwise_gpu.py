@@ -185,3 +185,73 @@ def test_depthwise_convblock_trains_like_fp64(cuda):
     assert _rel(y, yr.detach()) < 2e-5
     assert _rel(blk[1].running_mean, ref[1].running_mean) < 1e-5
     assert _rel(blk[1].running_var, ref[1].running_var) < 1e-5
+
+
+@pytest.mark.parametrize('relu', (False, True), ids=['plain', 'relu'])
+def test_mixed_requires_grad_gives_the_same_bits_and_none_elsewhere(cuda, relu):
+    """x only (no workspace, x not saved), weight only, bias only: each gradient equals the all-gradients call's bit for bit"""
+    from ever_amd.hip import functional as HF
+    p = dict(c=96, kh=3, kw=5, stride=(2, 1), pad=(1, 3), dil=(1, 2), n=2, h=13, w=18, bias=True, relu=relu)
+    x, w, b, g = _tensors(p, 21)
+    full = _hip(cuda, x, w, b, p['stride'], p['pad'], p['dil'], relu, g)
+    ref = _reference(x, w, b, p['stride'], p['pad'], p['dil'], relu, g)
+    for a, r, tol in zip(full, ref, (2e-6, 2e-6, 5e-6, 5e-6)):
+        assert _rel(a, r) < tol
+    for which in range(3):
+        leaves = [_nhwc(x, cuda), w.to(cuda), b.to(cuda)]
+        leaves[which].requires_grad_()
+        y = HF.depthwise_conv2d(*leaves, p['stride'], p['pad'], p['dil'], relu=relu)
+        y.backward(_nhwc(g, cuda))
+        torch.cuda.synchronize()
+        assert torch.equal(y.detach(), full[0])
+        for i, leaf in enumerate(leaves):
+            if i == which:
+                assert leaf.grad is not None and leaf.grad.shape == leaf.shape and torch.equal(leaf.grad, full[1 + i]), which
+            else:
+                assert leaf.grad is None
+    # no gradient at all: the output does not require one
+    assert not HF.depthwise_conv2d(_nhwc(x, cuda), w.to(cuda), b.to(cuda), p['stride'], p['pad'], p['dil'], relu=relu).requires_grad
+
+
+def test_non_dense_weight_view(cuda):
+    """a [C, 1, 3, 3] view with strides (18, 18, 6, 2): as a view of a parameter (the gradient reaches the parameter, zero between
+    the taps) and as a leaf of its own (the gradient has the leaf's shape)"""
+    from ever_amd.hip import functional as HF
+    c = 32
+    gen = torch.Generator().manual_seed(8)
+    x = torch.randn(2, c, 9, 11, generator=gen)
+    base = torch.randn(c, 1, 3, 6, generator=gen) * 0.3
+    g = torch.randn(2, c, 9, 11, generator=gen)
+    ref = _reference(x, base[..., ::2].contiguous(), None, 1, 1, 1, False, g)
+    param = base.to(cuda).requires_grad_()
+    view = param[..., ::2]
+    assert not view.is_contiguous() and view.shape == (c, 1, 3, 3)
+    y = HF.depthwise_conv2d(_nhwc(x, cuda), view, None, 1, 1, 1)
+    y.backward(_nhwc(g, cuda))
+    torch.cuda.synchronize()
+    assert _rel(y.detach(), ref[0]) < 2e-6
+    assert param.grad.shape == param.shape and bool((param.grad[..., 1::2] == 0).all())
+    assert _rel(param.grad[..., ::2], ref[2]) < 5e-6
+    leaf = base.to(cuda)[..., ::2].detach().requires_grad_()
+    assert leaf.stride() == (18, 18, 6, 2)
+    HF.depthwise_conv2d(_nhwc(x, cuda), leaf, None, 1, 1, 1).backward(_nhwc(g, cuda))
+    torch.cuda.synchronize()
+    assert leaf.grad.shape == leaf.shape and torch.equal(leaf.grad, param.grad[..., ::2])
+
+
+def test_broadcast_hw_backward_matches_fp64(cuda):
+    """the adjoint of the 1x1-map broadcast: dx[n][c] = sum over the pixels of g; at most ceil(HW / 32) + 32 roundings, each
+    relative to a partial sum of magnitude <= sum |g| (sum_hw_kernel: 32 pixel slices per channel group at C / 4 >= 8)"""
+    from ever_amd.hip import functional as HF
+    n, c, h, w = 3, 36, 17, 23
+    gen = torch.Generator().manual_seed(12)
+    x = torch.randn(n, c, 1, 1, generator=gen)
+    g = torch.randn(n, c, h, w, generator=gen)
+    xg = x.to(cuda).requires_grad_()
+    y = HF.broadcast_hw(xg, (h, w))
+    assert y.shape == (n, c, h, w) and torch.equal(y.detach().cpu(), x.expand(n, c, h, w))
+    y.backward(_nhwc(g, cuda))
+    torch.cuda.synchronize()
+    want = g.double().sum((2, 3), keepdim=True)
+    bound = (-(-h * w // 32) + 32) * 2.0 ** -24 * g.double().abs().sum((2, 3), keepdim=True)
+    assert xg.grad.shape == x.shape and bool(((xg.grad.double().cpu() - want).abs() <= bound).all())
