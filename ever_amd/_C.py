@@ -214,6 +214,12 @@ SIGNATURES = {
     'evk_scale_residual_fwd': (c_int, [P, P, P, P, P, c_i32, c_i64, c_i32, P]),
     'evk_scale_residual_bwd_workspace_bytes': (c_size_t, [c_i32, c_i64, c_i32]),
     'evk_scale_residual_bwd': (c_int, [P, P, P, P, P, P, c_i32, c_i64, c_i32, P, c_size_t, P]),
+    'evk_attn_plan': (c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
+    'evk_attn_fwd': (c_int, [P, P, P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_attn_bwd_workspace_bytes': (c_size_t, [c_i32, c_i32, c_i32, c_i32]),
+    'evk_attn_bwd': (c_int, [P, P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P, c_size_t, P]),
+    'evk_tokens_prepend_fwd': (c_int, [P, P, P, c_i32, c_i64, c_i32, c_i32, P]),
+    'evk_tokens_prepend_bwd': (c_int, [P, P, P, c_i32, c_i64, c_i32, c_i32, P]),
 }
 
 _lib = None

@@ -17,6 +17,7 @@ The wrappers live in one module per kernel family (round 6: this file used to ho
   transform.py   test-time augmentation: the eight symmetries of the square as one copy, their fused mean
   augment.py     input preparation: dihedral op, crop, normalisation and padding of a whole batch as one launch
   rownorm.py     LayerNorm over the channels of a map or the last axis of a token matrix, the layer-scale residual
+  attention.py   multi-head self-attention with RoPE on the QKV Linear's output, the token prefix of a ViT
 and every name of theirs is visible here, so `from ever_amd.hip import functional as HF; HF.conv2d(...)` and the
 `HF._X` switches that tests and tools read and set keep working: reading goes through this module's own dictionary (filled
 once at import), ASSIGNING `HF.name = value` is forwarded to every family module that holds `name` (a flag defined in
@@ -27,17 +28,18 @@ Reference call sites replaced (ever/module/...): see the per-function docstrings
 import sys
 import types
 
-from . import _base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm
+from . import _base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention
 
 __all__ = [
     'HipPathError', 'empty_nhwc', 'as_nhwc', 'is_nhwc', 'image_to_nhwc', 'conv2d', 'conv2d_fork', 'conv_transpose2d', 'batch_norm_act', 'relu',
     'max_pool3x3s2', 'upsample_nearest2x_add', 'upsample_bilinear', 'global_avg_pool', 'fs_relation',
     'mean4', 'add', 'bce_with_logits', 'dice_loss_with_logits', 'cross_entropy', 'soft_cross_entropy',
     'depthwise_conv2d', 'broadcast_hw', 'hr_fuse', 'bilinear_concat', 'd4', 'd4_mean', 'weighted_fuse', 'upsample_nearest2x',
-    'd4_compose', 'augment_batch', 'layer_norm', 'scale_residual', 'drop_path_scale',
+    'd4_compose', 'augment_batch', 'layer_norm', 'scale_residual', 'drop_path_scale', 'attention',
+    'prepend_tokens',
 ]
 
-_PARTS = (_base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm)
+_PARTS = (_base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention)
 for _m in _PARTS:            # later families win: conv.conv2d (the traceable wrapper) over nothing, pointwise.relu over _base's none
     for _k, _v in vars(_m).items():
         if not (_k.startswith('__') and _k.endswith('__')):

@@ -17,6 +17,7 @@ from .layers import (AdaptiveAvgPool2d, BatchNorm2d, Conv2d, ConvTranspose2d, Hi
                      UpsamplingBilinear2d, to_hip)
 from .ops import Bf16compatible, ConvBlock, ConvUpsampling, DepthwiseConv2d, PoolBlock, SeparableConv2d, SeparableConvBlock
 from .resnet import ResNetEncoder
+from .vit_encoder import ViTEncoder
 
 __all__ = ['ResNetEncoder', 'FPN', 'AssymetricDecoder', 'FSRelation', 'FSRelationV2', 'FarSegHead', 'FarSegPPHead', 'FarSeg', 'FarSegPP', 'FreeNet', 'ChangeMixin', 'ChangeStarFarSeg', 'ConvBlock',
            'Bf16compatible', 'ConvUpsampling', 'Conv2d', 'ConvTranspose2d', 'BatchNorm2d', 'ReLU', 'MaxPool2d', 'UpsamplingBilinear2d',
@@ -25,4 +26,4 @@ __all__ = ['ResNetEncoder', 'FPN', 'AssymetricDecoder', 'FSRelation', 'FSRelatio
            'Deeplabv3pDecoder', 'Deeplabv3pHead', 'DeepLabV3Plus',
            'HighResolutionModule', 'HighResolutionNet', 'HRNetEncoder', 'SimpleFusion', 'HRNetHead', 'HRNetSeg',
            'Fusion', 'FastNormalizedFusionConv3x3', 'NormalizedFusionConv3x3', 'BiFPN',
-           'LayerNorm', 'ConvNeXtEncoder', 'dinov3']
+           'LayerNorm', 'ConvNeXtEncoder', 'dinov3', 'ViTEncoder']

@@ -923,6 +923,36 @@ int evk_scale_residual_bwd(const float* dy, const float* z, const float* gamma, 
                            float* dgamma, int32_t N, int64_t HW, int32_t C, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ------------------------------------------------------------------ RoPE self-attention, token prefix --- */
+/* Multi-head self-attention with axial RoPE on Q and K — reference dinov3/layers/attention.py:16-27,66-85,106-118.
+ * qkv [B][N][3][H][D] fp32 (the QKV Linear's output as it lies), o [B][N][H*D] (what the projection Linear takes), scale
+ * 1/sqrt(D), softmax over all N keys, exact fp32 MFMA under every arithmetic mode.  The first `prefix` tokens are not
+ * rotated; token n >= prefix takes row n - prefix of sin / cos [N - prefix][D]: y = x cos + rotate_half(x) sin,
+ * rotate_half([x1, x2]) = [-x2, x1] over the halves of D.  sin == cos == NULL: no RoPE; prefix == N: no rotated token.
+ * Scope: D in {32, 64} (else EVK_E_UNSUPPORTED), H * D % 4 == 0, B, H, N >= 1, 0 <= prefix <= N, 16-byte aligned pointers
+ * (else EVK_E_INVALID); all refused before a launch.
+ * evk_attn_plan (host only): out = {query tile Tq, key tile Tk, key trips ceil(N / Tk), workgroups of each tiled kernel,
+ * LDS bytes of the forward and dQ kernels, LDS bytes of the dK / dV kernel}; it refuses what the launches refuse. */
+int evk_attn_plan(int32_t B, int32_t N, int32_t H, int32_t D, int32_t prefix, int32_t* out /*[6]*/);
+/* lse [B][H][N] (log-sum-exp of the scaled logits, what the backward recomputes P from) may be NULL: inference. */
+int evk_attn_fwd(const float* qkv, const float* sin, const float* cos, float* o, float* lse, int32_t B, int32_t N, int32_t H,
+                 int32_t D, int32_t prefix, void* stream);
+/* Host only: bytes of delta [B][N][H] = rowsum(do * o), written by a pre-pass of evk_attn_bwd (0 out of scope). */
+size_t evk_attn_bwd_workspace_bytes(int32_t B, int32_t N, int32_t H, int32_t D);
+/* dqkv [B][N][3][H][D]: the gradient with respect to the UN-rotated q and k (the adjoint of the rotation is general: any
+ * sin / cos) and v; every element is written.  One kernel owns a key tile for dK / dV, one a query tile for dQ; no float
+ * atomics, the same bits every run.  dqkv == NULL: nothing to do. */
+int evk_attn_bwd(const float* qkv, const float* sin, const float* cos, const float* o, const float* d_o, const float* lse,
+                 float* dqkv, int32_t B, int32_t N, int32_t H, int32_t D, int32_t prefix, void* workspace,
+                 size_t workspace_bytes, void* stream);
+/* out [B][P + HW][C] = cat(prefix [P][C] broadcast over the batch, patch [B][HW][C]) — prepare_tokens_with_masks without
+ * masks (dinov3/models/vision_transformer.py:201-231).  P >= 1, C % 4 == 0, 16-byte aligned pointers. */
+int evk_tokens_prepend_fwd(const float* patch, const float* prefix, float* out, int32_t B, int64_t HW, int32_t P, int32_t C,
+                           void* stream);
+/* dpatch [B][HW][C] (may be NULL) and dprefix [P][C] = sum over b, in batch order, of dout[b][:P] (may be NULL). */
+int evk_tokens_prepend_bwd(const float* dout, float* dpatch, float* dprefix, int32_t B, int64_t HW, int32_t P, int32_t C,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

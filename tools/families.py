@@ -34,6 +34,9 @@ FAMILIES = (
      ('^depthwise_',)),
     ('ln', 'row LayerNorm and layer-scale residual (ln_fwd / ln_bwd / ln_records_finalize, lscale_fwd / lscale_bwd kernels)',
      ('^ln_', '^lscale_')),
+    ('attention', 'self-attention with RoPE on the fp32 MFMA and the ViT token prefix (attn_fwd / attn_delta / attn_bwd_dkv / '
+     'attn_bwd_dq, tokens_prepend_* / tokens_prefix_grad kernels)',
+     ('^attn_', '^tokens_')),
     ('operand_prep', 'operand preparation of the f16x2 arithmetic (absmax* scale words, split_weight* planes)',
      ('^absmax', '^split_weight', '^pack_dgrad_weight', '^stem_s2d_weight', '^group_weight')),
     ('optimizer', 'fused optimizer / gradient-bucket kernels (sgd_multi, sqnorm_multi, pack_multi, clip)', ('^sgd_', '^adam_', '^sqnorm_', '^pack_multi', '^clip_', '^unpack_multi', '^scale_multi')),
