@@ -18,6 +18,7 @@ The wrappers live in one module per kernel family (round 6: this file used to ho
   augment.py     input preparation: dihedral op, crop, normalisation and padding of a whole batch as one launch
   rownorm.py     LayerNorm over the channels of a map or the last axis of a token matrix, the layer-scale residual
   attention.py   multi-head self-attention with RoPE on the QKV Linear's output, the token prefix of a ViT
+  stitch.py      whole-scene tiled inference: window scores added into a scene accumulator, mean scores or a class map from it
 and every name of theirs is visible here, so `from ever_amd.hip import functional as HF; HF.conv2d(...)` and the
 `HF._X` switches that tests and tools read and set keep working: reading goes through this module's own dictionary (filled
 once at import), ASSIGNING `HF.name = value` is forwarded to every family module that holds `name` (a flag defined in
@@ -28,7 +29,7 @@ Reference call sites replaced (ever/module/...): see the per-function docstrings
 import sys
 import types
 
-from . import _base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention
+from . import _base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention, stitch
 
 __all__ = [
     'HipPathError', 'empty_nhwc', 'as_nhwc', 'is_nhwc', 'image_to_nhwc', 'conv2d', 'conv2d_fork', 'conv_transpose2d', 'batch_norm_act', 'relu',
@@ -36,10 +37,10 @@ __all__ = [
     'mean4', 'add', 'bce_with_logits', 'dice_loss_with_logits', 'cross_entropy', 'soft_cross_entropy',
     'depthwise_conv2d', 'broadcast_hw', 'hr_fuse', 'bilinear_concat', 'd4', 'd4_mean', 'weighted_fuse', 'upsample_nearest2x',
     'd4_compose', 'augment_batch', 'layer_norm', 'scale_residual', 'drop_path_scale', 'attention',
-    'prepend_tokens',
+    'prepend_tokens', 'stitch_add', 'stitch_finalize',
 ]
 
-_PARTS = (_base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention)
+_PARTS = (_base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention, stitch)
 for _m in _PARTS:            # later families win: conv.conv2d (the traceable wrapper) over nothing, pointwise.relu over _base's none
     for _k, _v in vars(_m).items():
         if not (_k.startswith('__') and _k.endswith('__')):

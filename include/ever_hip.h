@@ -611,6 +611,40 @@ int evk_augment_plan(int32_t Hs, int32_t Ws, int32_t C, int32_t op, int32_t y0, 
  * op) and follows its own rule elsewhere; any other value, -1 by custom, restores the rule.  Returns the previous setting. */
 int evk_augment_force_kernel(int32_t kernel);
 
+/* Whole-scene tiled inference, the stitching half (csrc/stitch.hip; magic/bigimage/scene.py) — per window the
+ * `out[:, y0:y1, x0:x1] += s; count[y0:y1, x0:x1] += 1` of a sliding-window driver, per scene its `out / count`.
+ * scores: M window maps of one size h x w, acc: the scene accumulator, both in the same dense layout: NHWC memory (nchw == 0:
+ * scores [M,h,w,C], acc [H,W,C]) or NCHW-contiguous (scores [M,C,h,w], acc [C,H,W]); count: the coverage plane [H,W] fp32.
+ * `records` (HOST, read during the call) and `table` (DEVICE, read by the kernels; the caller uploads it in stream order) hold
+ * the same M records of 2 int64: { y0, x0 }, window m covers rows y0 .. y0+h-1 and columns x0 .. x0+w-1.
+ * Every accumulator element has ONE owner, which adds the windows that cover it in table order: ((acc + s_a) + s_b) + ..., the
+ * bits of the sequential loop; no atomics, two runs give the same bits.  The coverage of a pixel grows by 1 per covering window
+ * (added as one (float)n: the same value while the count is below 2^24).  The grid covers the bounding box of the windows of a
+ * launch; an element of the box that no window covers is neither read nor written.  64 windows per launch; a longer table is
+ * chained in order inside the call.  Element offsets are 64-bit: the accumulator may hold 2^31 elements or more.
+ * Refused before any launch: -1 for a null pointer, M < 1, a non-positive size, a window not inside the scene; -2 for
+ * C > 65535 or a scene row of 2^31 floats or more. */
+int evk_stitch_add(const int64_t* records, const int64_t* table, int32_t M, const float* scores, float* acc, float* count,
+                   int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, int32_t nchw, void* stream);
+/* One pass over acc and count (layouts as above).  mode 0, scores: out[i] = acc[i] / count[pixel of i], one correctly rounded
+ * division (0/0 = NaN where nothing was added); out: fp32 in acc's layout, NULL or acc itself for in place.  mode 1, labels:
+ * out [H,W] uint8 (label_i64 == 0) or int64; C >= 2: the index of the first maximal quotient acc / count — the quotients are
+ * compared, not the sums, and a NaN is maximal, as in torch.argmax; C == 1: quotient > threshold ? 1 : 0 (threshold is
+ * ignored otherwise); a pixel with coverage 0 gets fill_label.
+ * Refused before any launch: -1 for a null acc or count, labels without an output, a mode outside 0..1, a non-positive size,
+ * a fill_label outside 0..255 with uint8 labels; -2 for C > 256 with uint8 labels, C > 65535, a row of 2^31 floats or more. */
+int evk_stitch_finalize(float* acc, const float* count, int32_t C, int32_t H, int32_t W, int32_t nchw, int32_t mode, void* out,
+                        int32_t label_i64, float threshold, int32_t fill_label, void* stream);
+/* Host only, no launch: the checks evk_stitch_add makes on a table (same return codes) and the forms the kernels take for
+ * pointers on the 16-byte grid (the launchers fall back to the scalar forms otherwise).  out[12] = { stitch_add takes 16-byte
+ * items (every row start and every window edge on the 4-float grid: W*cpp, w*cpp and every x0*cpp multiples of 4, cpp = 1 for
+ * NCHW and C for NHWC), workgroups along a row of the bounding box (64 items each), workgroups down its rows (4 rows each),
+ * grid.y (planes: C for NCHW, 1 for NHWC), launches (ceil(M / 64)), bounding box y0, x0, y1, x1 (end exclusive), scores
+ * finalise takes 16-byte items (W*cpp % 4 == 0), labels finalise takes its wide form (4 pixels per thread: NCHW or C == 1 with
+ * W % 4 == 0; 16-byte channel loads: NHWC with C % 4 == 0), 0 }.  Numbers one, two and five to eight are those of the first launch. */
+int evk_stitch_plan(const int64_t* records, int32_t M, int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, int32_t nchw,
+                    int32_t* out);
+
 /* F.adaptive_avg_pool2d(x, 1) — fs_relation.py:177. x: [N,HW,C] -> y: [N,C]. */
 int evk_gap_fwd(const float* x, float* y, int32_t N, int32_t HW, int32_t C, void* stream);
 int evk_gap_bwd(const float* dy, float* dx, int32_t N, int32_t HW, int32_t C, void* stream);
