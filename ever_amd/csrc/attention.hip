@@ -328,7 +328,6 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dq_kernel(const float* 
   attn_store_grad<D>(dqkv + ((int64_t)b * a.N + q) * stride + (int64_t)h * D, dq, q, g, a, rot);
 }
 
-static inline bool attn_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // what every entry point refuses, before a launch
 static int attn_shape_check(const char* what, int32_t B, int32_t N, int32_t H, int32_t D, int32_t prefix) {
@@ -345,7 +344,7 @@ static int attn_shape_check(const char* what, int32_t B, int32_t N, int32_t H, i
 
 static int attn_rope_check(const char* what, const float* sin, const float* cos) {
   EVK_REQUIRE((sin == nullptr) == (cos == nullptr), EVK_E_INVALID, "%s: sin and cos come together or not at all", what);
-  EVK_REQUIRE(attn_aligned16(sin) && attn_aligned16(cos), EVK_E_INVALID, "%s: sin and cos must be 16-byte aligned", what);
+  EVK_REQUIRE(aligned16(sin) && aligned16(cos), EVK_E_INVALID, "%s: sin and cos must be 16-byte aligned", what);
   return EVK_OK;
 }
 
@@ -373,7 +372,7 @@ extern "C" int evk_attn_fwd(const float* qkv, const float* sin, const float* cos
   if (rc) return rc;
   EVK_REQUIRE(qkv && o, EVK_E_INVALID, "attn_fwd: null pointer");
   if ((rc = attn_rope_check("attn_fwd", sin, cos))) return rc;
-  EVK_REQUIRE(attn_aligned16(qkv) && attn_aligned16(o), EVK_E_INVALID, "attn_fwd: qkv and o must be 16-byte aligned");
+  EVK_REQUIRE(aligned16(qkv) && aligned16(o), EVK_E_INVALID, "attn_fwd: qkv and o must be 16-byte aligned");
   const int tiles = ceil_div(N, kAttnTile);
   const AttnDims a{N, H, prefix, prefix < N ? sin : nullptr, prefix < N ? cos : nullptr};
   const float scale = (float)(1.0 / sqrt((double)D));
@@ -399,7 +398,7 @@ extern "C" int evk_attn_bwd(const float* qkv, const float* sin, const float* cos
   if (!dqkv) return EVK_OK;   // nothing asked for
   EVK_REQUIRE(qkv && o && d_o && lse, EVK_E_INVALID, "attn_bwd: null pointer");
   if ((rc = attn_rope_check("attn_bwd", sin, cos))) return rc;
-  EVK_REQUIRE(attn_aligned16(qkv) && attn_aligned16(o) && attn_aligned16(d_o) && attn_aligned16(dqkv) && attn_aligned16(workspace),
+  EVK_REQUIRE(aligned16(qkv) && aligned16(o) && aligned16(d_o) && aligned16(dqkv) && aligned16(workspace),
               EVK_E_INVALID, "attn_bwd: qkv, o, do, dqkv and the workspace must be 16-byte aligned");
   const size_t need = evk_attn_bwd_workspace_bytes(B, N, H, D);
   EVK_REQUIRE(workspace && workspace_bytes >= need, EVK_E_WORKSPACE, "attn_bwd: workspace of %zu bytes, %zu needed",

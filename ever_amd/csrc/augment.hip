@@ -16,7 +16,8 @@
 //            else an output element per thread.  A non-swap op maps output rows to input rows (reversed at most): both sides
 //            run along rows.  A swap op gathers one pixel per input row.
 //   tile     a workgroup owns T x T output pixels and stores 16 bytes per thread as well (Wo % 4 == 0), else 4.  A sample with a swap op stages the T x T source pixels they come from
-//            through LDS, read along INPUT rows and written along OUTPUT rows, exactly as d4_apply_tile_kernel; a sample
+//            through LDS, read along INPUT rows and written along OUTPUT rows, by d4_apply_tile_kernel's own code (the plan,
+//            the staging loop and the tile index arithmetic of csrc/d4_tile.hpp); a sample
 //            without one reads directly (its rows already run along the output's).  The launch takes this kernel when the plan
 //            of any sample names it (evk_augment_plan), as evk_d4_merge does for its terms.
 // The tile holds the raw values as fp32 words with row stride S = T*C + pad.  NHWC output: S == C (mod 32), the lanes of a
@@ -26,25 +27,21 @@
 // Sources are read a byte (uint8) or a word (fp32) at a time: there is no wide-load path, so no alignment is assumed.
 // Indices are 32-bit: the entry point refuses a sample or an output of 2^31 elements or more.
 #include <atomic>
-#include "common.hpp"
+#include "d4_tile.hpp"
 
 namespace evk {
 
 constexpr int kAugRecWords = 8;
-constexpr int kAugMaxC = 64;
-constexpr int kAugTileFloats = 5120;   // >= T * (T*C + 31) for every (C, T) of aug_tile_edge: 32*159, 16*287, 8*543
-constexpr int kAugPerThread = 16;      // >= T*T*C / 256
-constexpr int kAugMaskTile = 32 * 33;  // T <= 32
+constexpr int kAugMaskTile = 32 * 33;  // the label tile, T x (T + 1) int64 with T <= 32
 
 enum AugKernel { kAugDirect = 0, kAugTile = 1 };
 enum AugMask { kAugNoMask = 0, kAugMaskU8 = 1, kAugMaskU8ToI64 = 2, kAugMaskI64 = 3 };
 
 struct AugPlan {
-  int kernel, tile, stride, lds_bytes, per_thread;
+  int kernel;
+  D4TilePlan tile;   // the image tile; all 0 for the direct kernels
   int vec;       // 16-byte stores (direct: Ho*Wo % 4 == 0, tile: Wo % 4 == 0; the launcher also wants the outputs on the 16-byte grid)
 };
-
-static inline int aug_tile_edge(int C) { return C <= 4 ? 32 : C <= 16 ? 16 : 8; }
 
 // Which swap ops take the tile, measured with tools/bench_augment.py on 16 sources of 1024 x 1024 x C -> 16 x C x 512 x 512 with
 // uint8 labels, an MI355X (table in DESIGN 2.16; us per batch, tile against direct):
@@ -65,7 +62,7 @@ static int aug_plan(int Hs, int Ws, int C, int op, int y0, int x0, int ch, int c
                     AugPlan* pl) {
   EVK_REQUIRE(Hs > 0 && Ws > 0 && C > 0 && ch > 0 && cw > 0 && Ho > 0 && Wo > 0 && op >= 0 && op <= 7, EVK_E_INVALID,
               "augment: bad argument (non-positive size or op outside 0..7)");
-  EVK_REQUIRE(C <= kAugMaxC, EVK_E_UNSUPPORTED, "augment: %d channels (up to %d are implemented)", C, kAugMaxC);
+  EVK_REQUIRE(C <= kTileMaxC, EVK_E_UNSUPPORTED, "augment: %d channels (up to %d are implemented)", C, kTileMaxC);
   EVK_REQUIRE(ch <= Ho && cw <= Wo, EVK_E_INVALID, "augment: crop %d x %d is larger than the output %d x %d", ch, cw, Ho, Wo);
   const int64_t nsrc = (int64_t)Hs * Ws * C;
   EVK_REQUIRE(nsrc < 0x80000000LL, EVK_E_UNSUPPORTED, "augment: a source of %lld elements (fewer than 2^31 are implemented)",
@@ -83,13 +80,7 @@ static int aug_plan(int Hs, int Ws, int C, int op, int y0, int x0, int ch, int c
   *pl = AugPlan{};
   pl->kernel = k;
   pl->vec = want != 2 && (k == kAugDirect ? ((int64_t)Ho * Wo) % 4 == 0 : Wo % 4 == 0);
-  if (k == kAugTile) {
-    const int T = aug_tile_edge(C), TC = T * C, res = nchw ? 1 : C;
-    pl->tile = T;
-    pl->stride = TC + (((res - TC) % 32) + 32) % 32;
-    pl->lds_bytes = T * pl->stride * (int)sizeof(float) + kAugMaskTile * (int)sizeof(long long);
-    pl->per_thread = (T * TC + 255) / 256;
-  }
+  if (k == kAugTile) pl->tile = d4_tile_plan(C, nchw ? 1 : C);
   return EVK_OK;
 }
 
@@ -128,10 +119,7 @@ __device__ __forceinline__ float aug_normalize(float raw, const float* __restric
 __device__ __forceinline__ uint32_t aug_out_offset(const AugGeom& g, int n, int r, int c, int k) {
   return g.nchw ? (((uint32_t)n * g.C + k) * g.Ho + r) * g.Wo + c : (((uint32_t)n * g.Ho + r) * g.Wo + c) * g.C + k;
 }
-__device__ __forceinline__ void aug_store_label(void* __restrict__ out_mask, const AugGeom& g, uint32_t pix, long long label) {
-  if (g.mask_mode == kAugMaskU8) reinterpret_cast<uint8_t*>(out_mask)[pix] = (uint8_t)label;
-  else reinterpret_cast<long long*>(out_mask)[pix] = label;
-}
+__device__ __forceinline__ bool aug_labels_i64(const AugGeom& g) { return g.mask_mode != kAugMaskU8; }
 
 // Source pixel of window pixel (r, c), or false where the window lies past the source (raw value and label 0 there).
 __device__ __forceinline__ bool aug_src_pixel(const AugRec& rec, int r, int c, uint32_t& spix) {
@@ -139,8 +127,9 @@ __device__ __forceinline__ bool aug_src_pixel(const AugRec& rec, int r, int c, u
   const int Ht = (op & 1) ? rec.Ws : rec.Hs, Wt = (op & 1) ? rec.Hs : rec.Ws;
   const int a = rec.y0 + r, b = rec.x0 + c;
   if (a >= Ht || b >= Wt) return false;
-  const int rr = (op & 2) ? Ht - 1 - a : a, cc = (op & 4) ? Wt - 1 - b : b;
-  spix = (op & 1) ? (uint32_t)cc * rec.Ws + rr : (uint32_t)rr * rec.Ws + cc;
+  int sa, sb;
+  d4_source(op, a, b, Ht, Wt, sa, sb);
+  spix = (uint32_t)sa * rec.Ws + sb;
   return true;
 }
 // Value of output element (r, c, k) and, on request, the label of its pixel, read from the source directly.
@@ -170,25 +159,14 @@ __global__ __launch_bounds__(256) void augment_direct_kernel(const long long* __
   else { pix = fdiv(j, g.fC); k = j - pix * g.C; }
   const uint32_t r = fdiv(pix, g.fWo), c = pix - r * g.Wo;
   out[(uint32_t)n * HW * g.C + j] = aug_value(rec, g, mean, stdv, r, c, k);
-  if (g.mask_mode != kAugNoMask && k == 0) aug_store_label(out_mask, g, (uint32_t)n * HW + pix, aug_label(rec, g, r, c));
+  if (g.mask_mode != kAugNoMask && k == 0)
+    store_label(out_mask, aug_labels_i64(g), (uint32_t)n * HW + pix, aug_label(rec, g, r, c));
 }
 
 // Four consecutive output elements per thread, one 16-byte store (Ho*Wo a multiple of 4, outputs on the 16-byte grid): with a
 // 4-byte store per thread the pass is bound by the number of store instructions, not by bytes (table in DESIGN 2.16).  The
 // labels are work items of their own after the image's, four consecutive pixels each: one 4-byte store of uint8 labels or two
-// 16-byte stores of int64 ones.  Sources are still read element by element, at any address.
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
-// the labels of pixels o .. o+3 (o a multiple of 4, the label output on the 16-byte grid): one 4-byte or two 16-byte stores
-__device__ __forceinline__ void aug_store_labels4(void* __restrict__ out_mask, const AugGeom& g, size_t o, const long long (&l)[4]) {
-  if (g.mask_mode == kAugMaskU8) {
-    *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out_mask) + o) =
-        ((uint32_t)l[0] & 255u) | (((uint32_t)l[1] & 255u) << 8) | (((uint32_t)l[2] & 255u) << 16) | (((uint32_t)l[3] & 255u) << 24);
-  } else {
-    i64x2* p = reinterpret_cast<i64x2*>(reinterpret_cast<long long*>(out_mask) + o);
-    p[0] = i64x2{l[0], l[1]};
-    p[1] = i64x2{l[2], l[3]};
-  }
-}
+// 16-byte stores of int64 ones (store_labels4).  Sources are still read element by element, at any address.
 __global__ __launch_bounds__(256) void augment_direct_vec_kernel(const long long* __restrict__ table, const float* __restrict__ mean,
                                                                  const float* __restrict__ stdv, float* __restrict__ out,
                                                                  void* __restrict__ out_mask, const AugGeom g) {
@@ -224,53 +202,51 @@ __global__ __launch_bounds__(256) void augment_direct_vec_kernel(const long long
       l[i] = aug_label(rec, g, r, c);
       if (++c == (uint32_t)g.Wo) { c = 0; ++r; }
     }
-    aug_store_labels4(out_mask, g, (size_t)n * HW + pix, l);
+    store_labels4(out_mask, aug_labels_i64(g), (size_t)n * HW + pix, l);
   }
+}
+
+// ---- the tile kernel.  Element e of a workgroup's T x T output tile is (rl, cl, k) in the output's own memory order.
+__device__ __forceinline__ D4TileElem aug_tile_decode(int e, const AugGeom& g) {
+  return g.nchw ? d4_tile_decode_planar(e, g.T, g.fTT, g.fT) : d4_tile_decode(e, g.T, g.C, g.fTC, g.fC);
+}
+// Value and label of tile pixel (rl, cl) of the tile at (r0, c0): from the staged tiles inside the window, else read directly.
+__device__ __forceinline__ float aug_tile_value(const uint32_t* tile, bool staged, const AugRec& rec, const AugGeom& g,
+                                                const float* __restrict__ mean, const float* __restrict__ stdv, int r0, int c0,
+                                                int rl, int cl, int k) {
+  const int r = r0 + rl, c = c0 + cl;
+  if (staged && r < g.ch && c < g.cw)
+    return aug_normalize(__uint_as_float(tile[d4_tile_word(rec.op, g.T, g.S, g.C, rl, cl, k)]), mean, stdv, k);
+  return aug_value(rec, g, mean, stdv, r, c, k);
+}
+__device__ __forceinline__ long long aug_tile_label(const long long* mtile, bool staged, const AugRec& rec, const AugGeom& g,
+                                                    int r0, int c0, int rl, int cl) {
+  const int r = r0 + rl, c = c0 + cl;
+  if (staged && r < g.ch && c < g.cw) return mtile[d4_tile_word(rec.op, g.T, g.T + 1, 1, rl, cl, 0)];
+  return aug_label(rec, g, r, c);
 }
 
 __global__ __launch_bounds__(256) void augment_tile_kernel(const long long* __restrict__ table, const float* __restrict__ mean,
                                                            const float* __restrict__ stdv, float* __restrict__ out,
                                                            void* __restrict__ out_mask, const AugGeom g) {
-  __shared__ float tile[kAugTileFloats];
+  __shared__ uint32_t tile[kTileFloats];      // the raw values as fp32 words
   __shared__ long long mtile[kAugMaskTile];
   const int n = blockIdx.y;
   const AugRec rec = aug_rec(table, n);
-  const int T = g.T, C = g.C, TC = T * C, nel = T * TC, op = rec.op;
+  const int T = g.T, nel = T * T * g.C, op = rec.op;
   const uint32_t tr = fdiv(blockIdx.x, g.fTilesC);
   const int r0 = (int)tr * T, c0 = (int)(blockIdx.x - tr * g.fTilesC.div) * T;
   const bool masks = g.mask_mode != kAugNoMask;
   // uniform over the workgroup (one sample, one tile): so is the barrier
   const bool staged = (op & 1) && r0 < g.ch && c0 < g.cw;
   if (staged) {
-    // T = d4(S, op) with a swap: S's rows are T's columns.  Source rows alo .. alo+T-1, columns blo .. blo+T-1; what lies
-    // outside the source is stored as 0, which is the raw value the window has there.
-    const int Ht = rec.Ws, Wt = rec.Hs;
-    const int alo = (op & 4) ? Wt - (rec.x0 + c0) - T : rec.x0 + c0;
-    const int blo = (op & 2) ? Ht - (rec.y0 + r0) - T : rec.y0 + r0;
-#pragma unroll
-    for (int i = 0; i < kAugPerThread; ++i) {
-      const int e = threadIdx.x + 256 * i;
-      if (e < nel) {
-        const int ra = (int)fdiv((uint32_t)e, g.fTC), kk = e - ra * TC;
-        const int arow = alo + ra, f = blo * C + kk;
-        float v = 0.0f;
-        if (arow >= 0 && arow < rec.Hs && f >= 0 && f < rec.Ws * C) v = aug_load_raw(rec, g, (uint32_t)arow * rec.Ws * C + f);
-        tile[ra * g.S + kk] = v;
-      }
-    }
-    if (masks) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int e = threadIdx.x + 256 * i;
-        if (e < T * T) {
-          const int ra = (int)fdiv((uint32_t)e, g.fT), kb = e - ra * T;
-          const int arow = alo + ra, bcol = blo + kb;
-          long long v = 0;
-          if (arow >= 0 && arow < rec.Hs && bcol >= 0 && bcol < rec.Ws) v = aug_load_label(rec, g, (uint32_t)arow * rec.Ws + bcol);
-          mtile[ra * (T + 1) + kb] = v;
-        }
-      }
-    }
+    // The tile's origin in d4(S, op) is the crop origin further on; what lies outside the source is stored as 0, which is the
+    // raw value the window has there.
+    d4_tile_stage<kTilePerThread>(tile, op, T, g.C, g.S, g.fTC, rec.y0 + r0, rec.x0 + c0, rec.Hs, rec.Ws,
+                                  [&](uint32_t o) { return __float_as_uint(aug_load_raw(rec, g, o)); });
+    if (masks)      // the label tile: one-word pixels, T * T <= 4 * 256 of them
+      d4_tile_stage<4>(mtile, op, T, 1, T + 1, g.fT, rec.y0 + r0, rec.x0 + c0, rec.Hs, rec.Ws,
+                       [&](uint32_t o) { return aug_load_label(rec, g, o); });
   }
   __syncthreads();
   if (g.vec) {
@@ -278,36 +254,20 @@ __global__ __launch_bounds__(256) void augment_tile_kernel(const long long* __re
     // map or outside it as a whole), one 16-byte store.  The four LDS reads of a lane are 4 words apart from its neighbour's:
     // a 4-way bank conflict, derived and accepted — the tile's LDS traffic is a few percent of the kernel's time.
 #pragma unroll
-    for (int i = 0; i < kAugPerThread / 4; ++i) {
+    for (int i = 0; i < kTilePerThread / 4; ++i) {
       const int e = (threadIdx.x + 256 * i) * 4;
       if (e < nel) {
-        int rl, cl, k;
-        if (g.nchw) {
-          k = (int)fdiv((uint32_t)e, g.fTT);
-          const int p = e - k * T * T;
-          rl = (int)fdiv((uint32_t)p, g.fT);
-          cl = p - rl * T;
-        } else {
-          rl = (int)fdiv((uint32_t)e, g.fTC);
-          const int kk = e - rl * TC;
-          cl = (int)fdiv((uint32_t)kk, g.fC);
-          k = kk - cl * C;
-        }
+        const D4TileElem t = aug_tile_decode(e, g);
+        int rl = t.rl, cl = t.cl, k = t.ch;
         const int r = r0 + rl;
         if (r < g.Ho && c0 + cl < g.Wo) {
           const uint32_t off = aug_out_offset(g, n, r, c0 + cl, k);
           float v[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const int c = c0 + cl;
-            if (staged && r < g.ch && c < g.cw) {
-              const int al = (op & 4) ? T - 1 - cl : cl, bl = (op & 2) ? T - 1 - rl : rl;
-              v[q] = aug_normalize(tile[al * g.S + bl * C + k], mean, stdv, k);
-            } else {
-              v[q] = aug_value(rec, g, mean, stdv, r, c, k);
-            }
+            v[q] = aug_tile_value(tile, staged, rec, g, mean, stdv, r0, c0, rl, cl, k);
             if (g.nchw) ++cl;
-            else if (++k == C) { k = 0; ++cl; }
+            else if (++k == g.C) { k = 0; ++cl; }
           }
           *reinterpret_cast<f32x4*>(out + off) = f32x4{v[0], v[1], v[2], v[3]};
         }
@@ -315,58 +275,29 @@ __global__ __launch_bounds__(256) void augment_tile_kernel(const long long* __re
     }
     const int e = threadIdx.x * 4;      // the labels: four consecutive pixels of one tile row
     if (masks && e < T * T) {
-      const int rl = (int)fdiv((uint32_t)e, g.fT);
+      const int rl = (int)fdiv((uint32_t)e, g.fT), r = r0 + rl;
       int cl = e - rl * T;
-      const int r = r0 + rl;
       if (r < g.Ho && c0 + cl < g.Wo) {
         const size_t o = ((size_t)n * g.Ho + r) * g.Wo + c0 + cl;
         long long l[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q, ++cl) {
-          const int c = c0 + cl;
-          if (staged && r < g.ch && c < g.cw) {
-            const int al = (op & 4) ? T - 1 - cl : cl, bl = (op & 2) ? T - 1 - rl : rl;
-            l[q] = mtile[al * (T + 1) + bl];
-          } else {
-            l[q] = aug_label(rec, g, r, c);
-          }
-        }
-        aug_store_labels4(out_mask, g, o, l);
+        for (int q = 0; q < 4; ++q, ++cl) l[q] = aug_tile_label(mtile, staged, rec, g, r0, c0, rl, cl);
+        store_labels4(out_mask, aug_labels_i64(g), o, l);
       }
     }
     return;
   }
 #pragma unroll
-  for (int i = 0; i < kAugPerThread; ++i) {
+  for (int i = 0; i < kTilePerThread; ++i) {
     const int e = threadIdx.x + 256 * i;
     if (e < nel) {
-      int rl, cl, k;
-      if (g.nchw) {
-        k = (int)fdiv((uint32_t)e, g.fTT);
-        const int p = e - k * T * T;
-        rl = (int)fdiv((uint32_t)p, g.fT);
-        cl = p - rl * T;
-      } else {
-        rl = (int)fdiv((uint32_t)e, g.fTC);
-        const int kk = e - rl * TC;
-        cl = (int)fdiv((uint32_t)kk, g.fC);
-        k = kk - cl * C;
-      }
-      const int r = r0 + rl, c = c0 + cl;
+      const D4TileElem t = aug_tile_decode(e, g);
+      const int rl = t.rl, cl = t.cl, k = t.ch, r = r0 + rl, c = c0 + cl;
       if (r < g.Ho && c < g.Wo) {
-        const bool labels = masks && k == 0;
-        float v;
-        long long label = g.mask_pad;
-        if (staged && r < g.ch && c < g.cw) {
-          const int al = (op & 4) ? T - 1 - cl : cl, bl = (op & 2) ? T - 1 - rl : rl;
-          v = aug_normalize(tile[al * g.S + bl * C + k], mean, stdv, k);
-          if (labels) label = mtile[al * (T + 1) + bl];
-        } else {
-          v = aug_value(rec, g, mean, stdv, r, c, k);
-          if (labels) label = aug_label(rec, g, r, c);
-        }
-        out[aug_out_offset(g, n, r, c, k)] = v;
-        if (labels) aug_store_label(out_mask, g, ((uint32_t)n * g.Ho + r) * g.Wo + c, label);
+        out[aug_out_offset(g, n, r, c, k)] = aug_tile_value(tile, staged, rec, g, mean, stdv, r0, c0, rl, cl, k);
+        if (masks && k == 0)
+          store_label(out_mask, aug_labels_i64(g), ((uint32_t)n * g.Ho + r) * g.Wo + c,
+                      aug_tile_label(mtile, staged, rec, g, r0, c0, rl, cl));
       }
     }
   }
@@ -382,7 +313,9 @@ extern "C" int evk_augment_plan(int32_t Hs, int32_t Ws, int32_t C, int32_t op, i
   AugPlan pl;
   const int rc = aug_plan(Hs, Ws, C, op, y0, x0, crop_h, crop_w, Ho, Wo, src_f32 != 0, nchw != 0, &pl);
   if (rc != EVK_OK) return rc;
-  out[0] = pl.kernel; out[1] = pl.tile; out[2] = pl.stride; out[3] = pl.lds_bytes; out[4] = pl.per_thread; out[5] = pl.vec;
+  const D4TilePlan& t = pl.tile;      // the LDS of the tile kernel: the image tile and the label tile
+  out[0] = pl.kernel; out[1] = t.T; out[2] = t.S; out[4] = t.per_thread; out[5] = pl.vec;
+  out[3] = pl.kernel == kAugTile ? t.lds_floats * (int)sizeof(float) + kAugMaskTile * (int)sizeof(long long) : 0;
   return EVK_OK;
 }
 
@@ -424,11 +357,11 @@ extern "C" int evk_augment_batch(const int64_t* records, const int64_t* table, i
   g.fT = g.fTC = g.fTT = g.fTilesC = make_fastdiv(1);
   hipStream_t st = (hipStream_t)stream;
   const long long* tab = reinterpret_cast<const long long*>(table);
-  const bool wide_ok = g_aug_force.load(std::memory_order_relaxed) != 2 && ((uintptr_t)out & 15u) == 0 &&
-                       (mask_mode == kAugNoMask || ((uintptr_t)out_mask & 15u) == 0);
+  const bool wide_ok = g_aug_force.load(std::memory_order_relaxed) != 2 && aligned16(out) &&
+                       (mask_mode == kAugNoMask || aligned16(out_mask));
   if (any_tile) {
-    const int T = tile_pl.tile, tr = (Ho + T - 1) / T, tc = (Wo + T - 1) / T;
-    g.T = T; g.S = tile_pl.stride; g.vec = wide_ok && Wo % 4 == 0;
+    const int T = tile_pl.tile.T, tr = (Ho + T - 1) / T, tc = (Wo + T - 1) / T;
+    g.T = T; g.S = tile_pl.tile.S; g.vec = wide_ok && Wo % 4 == 0;
     g.fT = make_fastdiv((uint32_t)T); g.fTC = make_fastdiv((uint32_t)(T * C)); g.fTT = make_fastdiv((uint32_t)(T * T));
     g.fTilesC = make_fastdiv((uint32_t)tc);
     hipLaunchKernelGGL(augment_tile_kernel, dim3((unsigned)(tr * tc), (unsigned)N), dim3(256), 0, st, tab, mean, stdv, out,

@@ -46,6 +46,28 @@ constexpr int kWave = 64;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+
+// what every 16-byte load and store of a launch asks of its pointers
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// uint8 or int64 label maps: the label of pixel pix, and those of first_pix .. first_pix+3 (first_pix a multiple of 4, the map
+// on the 16-byte grid) as one 4-byte store or two 16-byte stores
+__device__ __forceinline__ void store_label(void* __restrict__ out, bool is_i64, size_t pix, long long value) {
+  if (is_i64) reinterpret_cast<long long*>(out)[pix] = value;
+  else reinterpret_cast<uint8_t*>(out)[pix] = (uint8_t)value;
+}
+__device__ __forceinline__ void store_labels4(void* __restrict__ out, bool is_i64, size_t first_pix, const long long (&l)[4]) {
+  if (is_i64) {
+    i64x2* p = reinterpret_cast<i64x2*>(reinterpret_cast<long long*>(out) + first_pix);
+    p[0] = i64x2{l[0], l[1]};
+    p[1] = i64x2{l[2], l[3]};
+  } else {
+    *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out) + first_pix) =
+        ((uint32_t)l[0] & 255u) | (((uint32_t)l[1] & 255u) << 8) | (((uint32_t)l[2] & 255u) << 16) | (((uint32_t)l[3] & 255u) << 24);
+  }
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -103,9 +125,8 @@ inline int pick_tile(int bm, int bn, F&& f) {
 // element j — so a writer that owns element j = wave-chunk * 64 + lane gets its four words from four wave ballots, and a
 // reader with ANY thread-to-element mapping fetches one aligned 16-byte group and shifts.
 __host__ __device__ inline size_t relu_bits_words(size_t n4) { return ((n4 + 63) / 64) * 8; }
-typedef uint32_t relu_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 relu_bits_mask(f32x4 g, const uint32_t* __restrict__ bits, size_t j) {
-  const relu_u32x4 w = *reinterpret_cast<const relu_u32x4*>(bits + (j >> 6) * 8 + ((j >> 5) & 1) * 4);
+  const u32x4 w = *reinterpret_cast<const u32x4*>(bits + (j >> 6) * 8 + ((j >> 5) & 1) * 4);
   const uint32_t b = (uint32_t)(j & 31);
   f32x4 o;
   o.x = ((w.x >> b) & 1u) ? g.x : 0.f;
@@ -119,10 +140,10 @@ __device__ __forceinline__ void relu_bits_store(uint32_t* __restrict__ bits, siz
   const uint64_t b0 = __ballot(p0), b1 = __ballot(p1), b2 = __ballot(p2), b3 = __ballot(p3);
   const int lane = threadIdx.x & 63;
   if (lane == 0)
-    *reinterpret_cast<relu_u32x4*>(bits + chunk * 8) = relu_u32x4{(uint32_t)b0, (uint32_t)b1, (uint32_t)b2, (uint32_t)b3};
+    *reinterpret_cast<u32x4*>(bits + chunk * 8) = u32x4{(uint32_t)b0, (uint32_t)b1, (uint32_t)b2, (uint32_t)b3};
   if (lane == 32)
-    *reinterpret_cast<relu_u32x4*>(bits + chunk * 8 + 4) =
-        relu_u32x4{(uint32_t)(b0 >> 32), (uint32_t)(b1 >> 32), (uint32_t)(b2 >> 32), (uint32_t)(b3 >> 32)};
+    *reinterpret_cast<u32x4*>(bits + chunk * 8 + 4) =
+        u32x4{(uint32_t)(b0 >> 32), (uint32_t)(b1 >> 32), (uint32_t)(b2 >> 32), (uint32_t)(b3 >> 32)};
 }
 
 

@@ -15,58 +15,46 @@
 // C <= 4, even C <= 16, C % 4 == 0 above).  For the other widths (5, 21, ...) some halves straddle two rows, where bl changes
 // and the words are no longer consecutive; and with a column flip and C not a divisor of 32 a half that starts inside a
 // pixel can meet a 2-way conflict.
+// The op, the tile plan (T, S, the LDS capacity and its compile-time check), the staging loop and a tile element's index
+// arithmetic are in csrc/d4_tile.hpp, shared with csrc/augment.hip.
 // Indices are 32-bit: the entry points refuse N*H*W*C >= 2^31.
 #include <atomic>
-#include "common.hpp"
+#include "d4_tile.hpp"
 
 namespace evk {
 
 constexpr int kD4MaxTerms = 16;
-constexpr int kD4TileMaxC = 64;        // widest pixel the tile kernels hold
-constexpr int kD4TileFloats = 5120;    // >= T * (T*C + 31) for every (C, T) of d4_tile_edge: 32*159, 16*287, 8*543
-constexpr int kD4PerThread = 16;       // >= T*T*C / 256: the tile kernels' elements (accumulators) per thread
 // Which swap terms take the tile kernel, measured with tools/bench_tta.py on [N, 512, 512, C], an MI355X (table in DESIGN
 // 2.14): the tile kernel copies at 3.4-3.7 TB/s whatever C is; the 16-byte element kernel at 3.2 (C = 4), 4.8 (8), 6.0 (16),
 // 5.4 (32), 4.9 (64) TB/s; the scalar element kernel at 1.7 (C = 1), 2.3 (3), 2.6 (6) and, forced, 3.0-3.5 (4, 8 ... 64) TB/s.
 // So the rule of d4_plan: a swap term whose pixel the 16-byte kernel can take (C % 4 == 0) goes to the tile up to
 // kD4TileVecC = 4 floats and to the 16-byte kernel above; a swap term only the scalar kernel could take (C % 4 != 0) goes to
-// the tile as far as the tile holds it (C <= kD4TileMaxC).  Of the widths off the 4-grid only 1, 3 and 6 were timed; that the
+// the tile as far as the tile holds it (C <= kTileMaxC).  Of the widths off the 4-grid only 1, 3 and 6 were timed; that the
 // tile stays ahead of the scalar kernel up to 64 rests on the forced rows of C = 8 ... 64 (3.4-3.6 against 3.0-3.5 TB/s).
 constexpr int kD4TileVecC = 4;
 
 enum D4Kernel { kD4Scalar = 0, kD4Vec = 1, kD4Tile = 2 };
 struct D4Plan {
   int kernel;
-  int tile;          // T: the tile is T x T pixels (0 for the element kernels)
-  int stride;        // S, in floats
-  int lds_bytes;
-  int per_thread;    // ceil(T*T*C / 256)
+  D4TilePlan tile;   // all 0 for the element kernels
 };
-
-static inline int d4_tile_edge(int C) { return C <= 4 ? 32 : C <= 16 ? 16 : 8; }
 
 // Which kernel a term of shape [N, Hi, Wi, C] under `op` takes: pure host arithmetic, shared by evk_d4_apply, evk_d4_merge
 // and evk_d4_plan.  evk_d4_force_kernel (tools/bench_tta.py and the tests; nothing in the package calls it) overrides the
 // rule wherever the forced kernel is legal.
 static std::atomic<int> g_d4_force{-1};
-static int d4_plan(int N, int Hi, int Wi, int C, int op, bool aligned16, D4Plan* pl) {
+static int d4_plan(int N, int Hi, int Wi, int C, int op, bool ptrs16, D4Plan* pl) {
   EVK_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && C > 0 && op >= 0 && op <= 7, EVK_E_INVALID,
               "d4: bad argument (non-positive size or op outside 0..7)");
   const int64_t total = (int64_t)N * Hi * Wi * C;
   EVK_REQUIRE(total < 0x80000000LL, EVK_E_UNSUPPORTED, "d4: %lld elements (fewer than 2^31 are implemented)", (long long)total);
-  const bool swap = op & 1, vec_ok = C % 4 == 0 && aligned16, tile_ok = swap && C <= kD4TileMaxC;
+  const bool swap = op & 1, vec_ok = C % 4 == 0 && ptrs16, tile_ok = swap && C <= kTileMaxC;
   int k = tile_ok && (C % 4 != 0 || C <= kD4TileVecC) ? kD4Tile : vec_ok ? kD4Vec : kD4Scalar;
   const int want = g_d4_force.load(std::memory_order_relaxed);
   if (want == kD4Scalar || (want == kD4Vec && vec_ok) || (want == kD4Tile && tile_ok)) k = want;
   *pl = D4Plan{};
   pl->kernel = k;
-  if (k == kD4Tile) {
-    const int T = d4_tile_edge(C), TC = T * C;
-    pl->tile = T;
-    pl->stride = TC + (((C - TC) % 32) + 32) % 32;
-    pl->lds_bytes = T * pl->stride * (int)sizeof(float);
-    pl->per_thread = (T * TC + 255) / 256;
-  }
+  if (k == kD4Tile) pl->tile = d4_tile_plan(C, C);
   return EVK_OK;
 }
 
@@ -85,13 +73,12 @@ __device__ __forceinline__ uint32_t d4_src(uint32_t j, const D4Geom& g, int op) 
   const uint32_t pix = fdiv(j, g.fcv), cb = j - pix * cv;
   const uint32_t t = fdiv(pix, g.fWo), c = pix - t * Wo;
   const uint32_t n = fdiv(t, g.fHo), r = t - n * Ho;
-  const uint32_t rr = (op & 2) ? Ho - 1 - r : r, cc = (op & 4) ? Wo - 1 - c : c;
-  // swap: x is [N, Wo, Ho, C] and (a, b) = (cc, rr);  else x is [N, Ho, Wo, C] and (a, b) = (rr, cc)
-  const uint32_t spix = (op & 1) ? (n * Wo + cc) * Ho + rr : (n * Ho + rr) * Wo + cc;
+  uint32_t a, b;
+  d4_source(op, r, c, Ho, Wo, a, b);
+  // swap: x is [N, Wo, Ho, C];  else x is [N, Ho, Wo, C]
+  const uint32_t spix = (op & 1) ? (n * Wo + a) * Ho + b : (n * Ho + a) * Wo + b;
   return spix * cv + cb;
 }
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // The copy, an element (V = 1: one word, V = 4: 16 bytes) per thread.  Words, not floats: every bit pattern survives.
 template <int V>
@@ -143,41 +130,18 @@ struct D4Tile {
   FastDiv fC, fTC, fTilesC, fTilesR;    // C, T*C, tiles per output row, tile rows per image
 };
 
-// Stage the input pixels of a SWAP term that the output tile reads: input rows alo .. alo+T-1 (x's rows are y's columns),
-// columns blo .. blo+T-1, read as T runs of T*C consecutive floats.  A ragged tile reads what exists and stores zeros.
+// Stage a SWAP term of image n: x's rows are y's columns, so x is [N, Wo, Ho, C].
 __device__ __forceinline__ void d4_stage(uint32_t* __restrict__ tile, const uint32_t* __restrict__ x, const D4Tile& g, int op,
                                          int n, int r0, int c0) {
-  const int T = g.T, C = g.C, TC = T * C, nel = T * TC;
-  const int Hi = g.Wo, Wi = g.Ho;
-  const int alo = (op & 4) ? g.Wo - c0 - T : c0;
-  const int blo = (op & 2) ? g.Ho - r0 - T : r0;
-#pragma unroll
-  for (int i = 0; i < kD4PerThread; ++i) {
-    const int e = threadIdx.x + 256 * i;
-    if (e < nel) {
-      const int ra = (int)fdiv((uint32_t)e, g.fTC), kk = e - ra * TC;
-      const int arow = alo + ra, f = blo * C + kk;
-      uint32_t v = 0;
-      if (arow >= 0 && arow < Hi && f >= 0 && f < Wi * C) v = x[((size_t)n * Hi + arow) * Wi * C + f];
-      tile[ra * g.S + kk] = v;
-    }
-  }
+  const uint32_t* xn = x + (size_t)n * g.Wo * g.Ho * g.C;
+  d4_tile_stage<kTilePerThread>(tile, op, g.T, g.C, g.S, g.fTC, r0, c0, g.Wo, g.Ho, [xn](uint32_t o) { return xn[o]; });
 }
 // element e of the output tile: its offset in y (or -1 outside the map) and the word of a staged swap term that holds it
-__device__ __forceinline__ bool d4_tile_elem(int e, const D4Tile& g, int n, int r0, int c0, int& rl, int& cl, int& ch,
-                                             uint32_t& off) {
-  const int TC = g.T * g.C;
-  rl = (int)fdiv((uint32_t)e, g.fTC);
-  const int kk = e - rl * TC;
-  cl = (int)fdiv((uint32_t)kk, g.fC);
-  ch = kk - cl * g.C;
-  const int r = r0 + rl, c = c0 + cl;
-  off = (((uint32_t)n * g.Ho + r) * g.Wo + c) * g.C + ch;      // < 2^31 inside the map, unused outside
+__device__ __forceinline__ bool d4_tile_elem(int e, const D4Tile& g, int n, int r0, int c0, D4TileElem& t, uint32_t& off) {
+  t = d4_tile_decode(e, g.T, g.C, g.fTC, g.fC);
+  const int r = r0 + t.rl, c = c0 + t.cl;
+  off = (((uint32_t)n * g.Ho + r) * g.Wo + c) * g.C + t.ch;      // < 2^31 inside the map, unused outside
   return r < g.Ho && c < g.Wo;
-}
-__device__ __forceinline__ int d4_tile_word(const D4Tile& g, int op, int rl, int cl, int ch) {
-  const int al = (op & 4) ? g.T - 1 - cl : cl, bl = (op & 2) ? g.T - 1 - rl : rl;
-  return al * g.S + bl * g.C + ch;
 }
 __device__ __forceinline__ void d4_tile_origin(const D4Tile& g, int& n, int& r0, int& c0) {
   const uint32_t b = blockIdx.x;
@@ -188,20 +152,20 @@ __device__ __forceinline__ void d4_tile_origin(const D4Tile& g, int& n, int& r0,
 
 __global__ __launch_bounds__(256) void d4_apply_tile_kernel(const uint32_t* __restrict__ x, uint32_t* __restrict__ y,
                                                             const D4Tile g, int op) {
-  __shared__ uint32_t tile[kD4TileFloats];
+  __shared__ uint32_t tile[kTileFloats];
   int n, r0, c0;
   d4_tile_origin(g, n, r0, c0);
   d4_stage(tile, x, g, op, n, r0, c0);
   __syncthreads();
   const int nel = g.T * g.T * g.C;
 #pragma unroll
-  for (int i = 0; i < kD4PerThread; ++i) {
+  for (int i = 0; i < kTilePerThread; ++i) {
     const int e = threadIdx.x + 256 * i;
     if (e < nel) {
-      int rl, cl, ch;
+      D4TileElem t;
       uint32_t off;
-      const bool in = d4_tile_elem(e, g, n, r0, c0, rl, cl, ch, off);
-      const uint32_t v = tile[d4_tile_word(g, op, rl, cl, ch)];     // the address is computed for every lane, the store masked
+      const bool in = d4_tile_elem(e, g, n, r0, c0, t, off);
+      const uint32_t v = tile[d4_tile_word(op, g.T, g.S, g.C, t.rl, t.cl, t.ch)];     // the address is computed for every lane, the store masked
       if (in) y[off] = v;
     }
   }
@@ -213,7 +177,7 @@ __global__ __launch_bounds__(256) void d4_apply_tile_kernel(const uint32_t* __re
 // The term loop is rolled; its tables are copied to LDS by constant indices first (see d4_merge_kernel).
 __global__ __launch_bounds__(256) void d4_merge_tile_kernel(const D4Terms a, int nterms, const float* acc, float* y,
                                                             const D4Tile g, int count) {
-  __shared__ uint32_t tile[kD4TileFloats];
+  __shared__ uint32_t tile[kTileFloats];
   __shared__ const float* sp[kD4MaxTerms];
   __shared__ uint32_t sop[kD4MaxTerms];
   if (threadIdx.x == 0) {
@@ -226,15 +190,15 @@ __global__ __launch_bounds__(256) void d4_merge_tile_kernel(const D4Terms a, int
   int n, r0, c0;
   d4_tile_origin(g, n, r0, c0);
   const int nel = g.T * g.T * g.C;
-  float s[kD4PerThread];
+  float s[kTilePerThread];
 #pragma unroll
-  for (int i = 0; i < kD4PerThread; ++i) {
+  for (int i = 0; i < kTilePerThread; ++i) {
     s[i] = 0.0f;
     const int e = threadIdx.x + 256 * i;
     if (acc && e < nel) {
-      int rl, cl, ch;
+      D4TileElem t;
       uint32_t off;
-      if (d4_tile_elem(e, g, n, r0, c0, rl, cl, ch, off)) s[i] = acc[off];
+      if (d4_tile_elem(e, g, n, r0, c0, t, off)) s[i] = acc[off];
     }
   }
   __syncthreads();
@@ -248,19 +212,19 @@ __global__ __launch_bounds__(256) void d4_merge_tile_kernel(const D4Terms a, int
       __syncthreads();
     }
 #pragma unroll
-    for (int i = 0; i < kD4PerThread; ++i) {
+    for (int i = 0; i < kTilePerThread; ++i) {
       const int e = threadIdx.x + 256 * i;
       if (e < nel) {
-        int rl, cl, ch;
+        D4TileElem t;
         uint32_t off;
-        const bool in = d4_tile_elem(e, g, n, r0, c0, rl, cl, ch, off);
+        const bool in = d4_tile_elem(e, g, n, r0, c0, t, off);
         float v = 0.0f;
         if (staged) {
-          v = __uint_as_float(tile[d4_tile_word(g, op, rl, cl, ch)]);
+          v = __uint_as_float(tile[d4_tile_word(op, g.T, g.S, g.C, t.rl, t.cl, t.ch)]);
         } else if (in) {
-          const int r = r0 + rl, c = c0 + cl;
-          const int rr = (op & 2) ? g.Ho - 1 - r : r, cc = (op & 4) ? g.Wo - 1 - c : c;
-          v = p[(((size_t)n * g.Ho + rr) * g.Wo + cc) * g.C + ch];
+          int rr, cc;       // a term that is not staged has no swap
+          d4_source(op & 6, r0 + t.rl, c0 + t.cl, g.Ho, g.Wo, rr, cc);
+          v = p[(((size_t)n * g.Ho + rr) * g.Wo + cc) * g.C + t.ch];
         }
         s[i] = s[i] + v;
       }
@@ -268,12 +232,12 @@ __global__ __launch_bounds__(256) void d4_merge_tile_kernel(const D4Terms a, int
   }
   const float d = (float)count;
 #pragma unroll
-  for (int i = 0; i < kD4PerThread; ++i) {
+  for (int i = 0; i < kTilePerThread; ++i) {
     const int e = threadIdx.x + 256 * i;
     if (e < nel) {
-      int rl, cl, ch;
+      D4TileElem t;
       uint32_t off;
-      if (d4_tile_elem(e, g, n, r0, c0, rl, cl, ch, off)) y[off] = count > 0 ? __fdiv_rn(s[i], d) : s[i];
+      if (d4_tile_elem(e, g, n, r0, c0, t, off)) y[off] = count > 0 ? __fdiv_rn(s[i], d) : s[i];
     }
   }
 }
@@ -282,12 +246,11 @@ static D4Geom d4_geom(int Ho, int Wo, int cv) {
   return D4Geom{make_fastdiv((uint32_t)cv), make_fastdiv((uint32_t)Wo), make_fastdiv((uint32_t)Ho)};
 }
 static D4Tile d4_tile_geom(int N, int Ho, int Wo, int C, const D4Plan& pl, unsigned* grid) {
-  const int T = pl.tile, tr = (Ho + T - 1) / T, tc = (Wo + T - 1) / T;
+  const int T = pl.tile.T, tr = (Ho + T - 1) / T, tc = (Wo + T - 1) / T;
   *grid = (unsigned)((int64_t)N * tr * tc);     // <= N*Ho*Wo < 2^31
-  return D4Tile{Ho, Wo, C, T, pl.stride, make_fastdiv((uint32_t)C), make_fastdiv((uint32_t)(T * C)),
+  return D4Tile{Ho, Wo, C, T, pl.tile.S, make_fastdiv((uint32_t)C), make_fastdiv((uint32_t)(T * C)),
                 make_fastdiv((uint32_t)tc), make_fastdiv((uint32_t)tr)};
 }
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace evk
 
@@ -298,7 +261,8 @@ extern "C" int evk_d4_plan(int32_t N, int32_t Hi, int32_t Wi, int32_t C, int32_t
   D4Plan pl;
   const int rc = d4_plan(N, Hi, Wi, C, op, true, &pl);
   if (rc != EVK_OK) return rc;
-  out[0] = pl.kernel; out[1] = pl.tile; out[2] = pl.tile; out[3] = pl.stride; out[4] = pl.lds_bytes; out[5] = pl.per_thread;
+  const D4TilePlan& t = pl.tile;
+  out[0] = pl.kernel; out[1] = t.T; out[2] = t.T; out[3] = t.S; out[4] = t.lds_floats * (int)sizeof(float); out[5] = t.per_thread;
   return EVK_OK;
 }
 

@@ -119,7 +119,7 @@ extern "C" int evk_scale_residual_fwd(const float* a, const float* z, const floa
   int rc = lscale_check("scale_residual_fwd", N, HW, C);
   if (rc) return rc;
   EVK_REQUIRE(a && z && y, EVK_E_INVALID, "scale_residual_fwd: null pointer");
-  EVK_REQUIRE(rg_aligned16(a) && rg_aligned16(z) && rg_aligned16(y) && rg_aligned16(gamma), EVK_E_INVALID,
+  EVK_REQUIRE(aligned16(a) && aligned16(z) && aligned16(y) && aligned16(gamma), EVK_E_INVALID,
               "scale_residual_fwd: a, z, y and gamma must be 16-byte aligned");
   const int64_t R = (int64_t)N * HW;
   const RowPlan p = row_plan(R, C);
@@ -143,8 +143,8 @@ extern "C" int evk_scale_residual_bwd(const float* dy, const float* z, const flo
   int rc = lscale_check("scale_residual_bwd", N, HW, C);
   if (rc) return rc;
   EVK_REQUIRE(dy && (dz || dgamma) && (z || !dgamma), EVK_E_INVALID, "scale_residual_bwd: null pointer");
-  EVK_REQUIRE(rg_aligned16(dy) && rg_aligned16(z) && rg_aligned16(gamma) && rg_aligned16(dz) && rg_aligned16(dgamma) &&
-                  rg_aligned16(workspace),
+  EVK_REQUIRE(aligned16(dy) && aligned16(z) && aligned16(gamma) && aligned16(dz) && aligned16(dgamma) &&
+                  aligned16(workspace),
               EVK_E_INVALID, "scale_residual_bwd: dy, z, gamma, dz, dgamma and the workspace must be 16-byte aligned");
   const size_t need = evk_scale_residual_bwd_workspace_bytes(N, HW, C);
   EVK_REQUIRE(!dgamma || (workspace && workspace_bytes >= need), EVK_E_WORKSPACE,

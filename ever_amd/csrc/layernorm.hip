@@ -184,7 +184,7 @@ extern "C" int evk_ln_fwd(const float* x, const float* gamma, const float* beta,
   int rc = row_shape_check("ln_fwd", R, C);
   if (rc) return rc;
   EVK_REQUIRE(x && y, EVK_E_INVALID, "ln_fwd: null pointer");
-  EVK_REQUIRE(rg_aligned16(x) && rg_aligned16(y) && rg_aligned16(gamma) && rg_aligned16(beta), EVK_E_INVALID,
+  EVK_REQUIRE(aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta), EVK_E_INVALID,
               "ln_fwd: x, y, gamma and beta must be 16-byte aligned");
   EVK_REQUIRE(eps >= 0.f, EVK_E_INVALID, "ln_fwd: negative eps");
   const RowPlan p = row_plan(R, C);
@@ -204,8 +204,8 @@ extern "C" int evk_ln_bwd(const float* dy, const float* x, const float* save_mea
   if (rc) return rc;
   EVK_REQUIRE(dy && x && save_mean && save_rstd, EVK_E_INVALID, "ln_bwd: null pointer");
   EVK_REQUIRE(dx || dgamma || dbeta, EVK_E_INVALID, "ln_bwd: no output requested");
-  EVK_REQUIRE(rg_aligned16(dy) && rg_aligned16(x) && rg_aligned16(gamma) && rg_aligned16(dx) && rg_aligned16(dgamma) &&
-                  rg_aligned16(dbeta) && rg_aligned16(workspace),
+  EVK_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(gamma) && aligned16(dx) && aligned16(dgamma) &&
+                  aligned16(dbeta) && aligned16(workspace),
               EVK_E_INVALID, "ln_bwd: dy, x, gamma, dx, dgamma, dbeta and the workspace must be 16-byte aligned");
   const bool params = dgamma || dbeta;
   EVK_REQUIRE(!params || (workspace && workspace_bytes >= evk_ln_bwd_workspace_bytes(R, C)), EVK_E_WORKSPACE,

@@ -55,7 +55,6 @@ inline int row_shape_check(const char* what, int64_t R, int32_t C) {
   EVK_REQUIRE(C % 4 == 0 && C <= kRgMaxC, EVK_E_UNSUPPORTED, "%s: C=%d must be a multiple of 4 in 4..%d", what, C, kRgMaxC);
   return EVK_OK;
 }
-inline bool rg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ f32x4 rg_ld(const float* p) { return *reinterpret_cast<const f32x4*>(p); }

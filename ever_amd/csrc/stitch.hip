@@ -22,6 +22,7 @@
 // added).  labels: per pixel the index of the first maximal QUOTIENT (two sums that differ can round to one quotient, so the
 // sums are not compared), a NaN maximal as in torch.argmax; with one class `quotient > threshold`; fill_label where the
 // coverage is 0.
+// The uint8 / int64 label stores are csrc/common.hpp's, shared with csrc/augment.hip.
 // Element offsets are 64-bit everywhere; what is 32-bit is an offset inside one row (RW < 2^31 is required).
 #include "common.hpp"
 
@@ -40,8 +41,6 @@ struct StitchPlan {
   int fin_vec;             // stitch_finalize, scores: 16-byte items
   int lab_vec;             // stitch_finalize, labels: 4 pixels per thread (cpp == 1) or 16-byte channel loads (cpp % 4 == 0)
 };
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 static int stitch_check_scene(int C, int H, int W, const char* what) {
   EVK_REQUIRE(C > 0 && H > 0 && W > 0, EVK_E_INVALID, "%s: non-positive size (C %d, H %d, W %d)", what, C, H, W);
@@ -190,12 +189,6 @@ __global__ __launch_bounds__(256) void stitch_scores_kernel(const float* acc, co
 __device__ __forceinline__ void stitch_best(float q, int k, float& best, int& idx) {
   if (q > best || (q != q && best == best)) { best = q; idx = k; }
 }
-__device__ __forceinline__ void stitch_store_label(void* __restrict__ out, int i64, size_t pix, int label) {
-  if (i64) reinterpret_cast<long long*>(out)[pix] = label;
-  else reinterpret_cast<uint8_t*>(out)[pix] = (uint8_t)label;
-}
-
-typedef long long stitch_i64x2 __attribute__((ext_vector_type(2)));
 
 // labels of planar maps (cpp == 1: NCHW-contiguous, or one class): PV consecutive pixels of a row per thread, class k of them
 // H*W floats further on.
@@ -239,17 +232,10 @@ __global__ __launch_bounds__(256) void stitch_labels_planar_kernel(const float* 
   for (int i = 0; i < PV; ++i)
     if (c[i] == 0.0f) idx[i] = g.fill;
   if constexpr (PV == 4) {
-    if (g.label_i64) {
-      stitch_i64x2* o = reinterpret_cast<stitch_i64x2*>(reinterpret_cast<long long*>(out) + pix);
-      o[0] = stitch_i64x2{idx[0], idx[1]};
-      o[1] = stitch_i64x2{idx[2], idx[3]};
-    } else {
-      *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out) + pix) =
-          ((uint32_t)idx[0] & 255u) | (((uint32_t)idx[1] & 255u) << 8) | (((uint32_t)idx[2] & 255u) << 16) |
-          (((uint32_t)idx[3] & 255u) << 24);
-    }
+    const long long l[4] = {idx[0], idx[1], idx[2], idx[3]};
+    store_labels4(out, g.label_i64, pix, l);
   } else {
-    stitch_store_label(out, g.label_i64, pix, idx[0]);
+    store_label(out, g.label_i64, pix, idx[0]);
   }
 }
 
@@ -279,7 +265,7 @@ __global__ __launch_bounds__(256) void stitch_labels_pixel_kernel(const float* _
     best = __fdiv_rn(a[0], c);
     for (int k = 1; k < g.C; ++k) stitch_best(__fdiv_rn(a[k], c), k, best, idx);
   }
-  stitch_store_label(out, g.label_i64, pix, c == 0.0f ? g.fill : idx);
+  store_label(out, g.label_i64, pix, c == 0.0f ? g.fill : idx);
 }
 
 static inline bool stitch_fin_vec(int W, int cpp) { return ((int64_t)W * cpp) % 4 == 0; }

@@ -43,7 +43,6 @@ static int tokens_check(const char* what, int32_t B, int64_t HW, int32_t P, int3
   return EVK_OK;
 }
 
-static inline bool tok_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline unsigned tok_grid(int64_t n) { return (unsigned)(n < (int64_t)kTokGridCap * 256 ? ceil_div(n, 256) : kTokGridCap); }
 
 }  // namespace evk
@@ -55,7 +54,7 @@ extern "C" int evk_tokens_prepend_fwd(const float* patch, const float* prefix, f
   int rc = tokens_check("tokens_prepend_fwd", B, HW, P, C);
   if (rc) return rc;
   EVK_REQUIRE(patch && prefix && out, EVK_E_INVALID, "tokens_prepend_fwd: null pointer");
-  EVK_REQUIRE(tok_aligned16(patch) && tok_aligned16(prefix) && tok_aligned16(out), EVK_E_INVALID,
+  EVK_REQUIRE(aligned16(patch) && aligned16(prefix) && aligned16(out), EVK_E_INVALID,
               "tokens_prepend_fwd: patch, prefix and out must be 16-byte aligned");
   const int64_t c4 = C / 4, hw4 = HW * c4, p4 = (int64_t)P * c4, total = B * (hw4 + p4);
   hipLaunchKernelGGL(tokens_prepend_fwd_kernel, dim3(tok_grid(total)), dim3(256), 0, (hipStream_t)stream,
@@ -70,7 +69,7 @@ extern "C" int evk_tokens_prepend_bwd(const float* dout, float* dpatch, float* d
   if (rc) return rc;
   if (!dpatch && !dprefix) return EVK_OK;
   EVK_REQUIRE(dout, EVK_E_INVALID, "tokens_prepend_bwd: null pointer");
-  EVK_REQUIRE(tok_aligned16(dout) && tok_aligned16(dpatch) && tok_aligned16(dprefix), EVK_E_INVALID,
+  EVK_REQUIRE(aligned16(dout) && aligned16(dpatch) && aligned16(dprefix), EVK_E_INVALID,
               "tokens_prepend_bwd: dout, dpatch and dprefix must be 16-byte aligned");
   const int64_t c4 = C / 4, hw4 = HW * c4, p4 = (int64_t)P * c4;
   hipStream_t st = (hipStream_t)stream;

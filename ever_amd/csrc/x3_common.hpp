@@ -8,7 +8,6 @@ namespace evk {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK3 = 32;             // fp32 K elements per step = two 32x32x16 MFMA k-blocks
 constexpr int kRowBytes = BK3 * 2;  // one LDS row of one bf16 plane

@@ -9,7 +9,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _C
-from . import timing, weight_planes
+from . import oplib, timing, weight_planes
 from .workspace import workspace
 
 
@@ -321,6 +321,23 @@ def _require_cuda(t, what):
         raise HipPathError(f'{what}: fp32 tensors required, got {t.dtype}')
 
 
+def _check_map(t, what, dim, dims, why_untraceable, done):
+    """what the inference-side families (hip/transform.py, hip/stitch.py) ask of a tensor: fp32 on the GPU, `dim`-D, not
+    packed, and no trace being recorded"""
+    _require_cuda(t, what)
+    if oplib.tracing():
+        raise HipPathError(f'{what}: not traceable ({why_untraceable})')
+    if t.dim() != dim:
+        raise HipPathError(f'{what}: a {dims} tensor is required, got {tuple(t.shape)}')
+    if _is_packed(t):
+        raise HipPathError(f'{what}: a packed activation (one convolution\'s private operand) cannot be {done}')
+
+
+def _inference_only(what, *ts):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise HipPathError(f'{what}: inference only (call it under torch.no_grad())')
+
+
 def empty_nhwc(n, c, h, w, device, dtype=torch.float32):
     """Logical [n,c,h,w] tensor over dense NHWC memory."""
     return torch.empty((n, h, w, c), device=device, dtype=dtype).permute(0, 3, 1, 2)
@@ -328,6 +345,11 @@ def empty_nhwc(n, c, h, w, device, dtype=torch.float32):
 
 def is_nhwc(t):
     return t.dim() == 4 and t.permute(0, 2, 3, 1).is_contiguous()
+
+
+def nhwc_copy(t):
+    """`t` [N, C, H, W] copied into dense NHWC memory by torch: any device, any dtype, no kernel of this package"""
+    return t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
 
 
 def as_nhwc(t, what='tensor'):

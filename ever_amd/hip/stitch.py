@@ -7,8 +7,7 @@ The accumulator is a 3-D logical [C, H, W] tensor in one of the two dense layout
 contiguous) or contiguous; window scores are [M, C, h, w] and are brought to the accumulator's layout if they are in the other."""
 import torch
 
-from . import oplib
-from ._base import HipPathError, _is_packed, _require_cuda, _stream, _timed_call
+from ._base import HipPathError, _check_map, _inference_only, _stream, _timed_call, nhwc_copy
 from .ptr_table import PtrTable
 
 __all__ = ['stitch_add', 'stitch_finalize', 'stitch_stats']
@@ -22,18 +21,7 @@ stitch_stats = {'add': 0, 'windows': 0, 'launches': 0, 'finalize': 0}      # tes
 
 
 def _check(t, what, dim):
-    _require_cuda(t, what)
-    if oplib.tracing():
-        raise HipPathError(f'{what}: not traceable (trace the model, not the tiling around it)')
-    if t.dim() != dim:
-        raise HipPathError(f'{what}: a {dim}-D tensor is required, got {tuple(t.shape)}')
-    if _is_packed(t):
-        raise HipPathError(f'{what}: a packed activation (one convolution\'s private operand) cannot be stitched')
-
-
-def _no_grad(what, *ts):
-    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
-        raise HipPathError(f'{what}: inference only (call it under torch.no_grad())')
+    _check_map(t, what, dim, f'{dim}-D', 'trace the model, not the tiling around it', 'stitched')
 
 
 def _acc_layout(acc, what):
@@ -60,7 +48,7 @@ def stitch_add(acc, count, scores, origins):
     _check(acc, 'stitch_add', 3)
     _check(scores, 'stitch_add', 4)
     _check_count(count, acc, 'stitch_add')
-    _no_grad('stitch_add', acc, count, scores)
+    _inference_only('stitch_add', acc, count, scores)
     m, c, h, w = scores.shape
     if m == 0 or len(origins) != m or c != acc.shape[0] or scores.device != acc.device:
         raise ValueError(f'stitch_add: scores {tuple(scores.shape)} on {scores.device} with {len(origins)} origins for an '
@@ -69,7 +57,7 @@ def stitch_add(acc, count, scores, origins):
     if nchw:
         scores = scores if scores.is_contiguous() else scores.contiguous()
     elif not scores.permute(0, 2, 3, 1).is_contiguous():
-        scores = scores.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+        scores = nhwc_copy(scores)
     vals = []
     for y0, x0 in origins:
         vals += [int(y0), int(x0)]
@@ -99,7 +87,7 @@ def stitch_finalize(acc, count, mode='scores', out=None, label_dtype=torch.uint8
     labels mode.  Returns the output.  No autograd; not traceable."""
     _check(acc, 'stitch_finalize', 3)
     _check_count(count, acc, 'stitch_finalize')
-    _no_grad('stitch_finalize', acc, count)
+    _inference_only('stitch_finalize', acc, count)
     c, h, w = acc.shape
     nchw = _acc_layout(acc, 'stitch_finalize')
     if mode == 'scores':

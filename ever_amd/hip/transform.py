@@ -10,8 +10,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import oplib
-from ._base import HipPathError, _is_packed, _ptr, _require_cuda, _stream, _timed_call, empty_nhwc, is_nhwc, materialize_lazy
+from ._base import _check_map, _inference_only, _ptr, _stream, _timed_call, empty_nhwc, is_nhwc, materialize_lazy, nhwc_copy
 
 __all__ = ['d4', 'd4_mean', 'd4_inverse', 'd4_compose', 'd4_out_hw', 'd4_stats', 'D4_IDENTITY', 'D4_TRANSPOSE', 'D4_VFLIP', 'D4_HFLIP',
            'D4_ROT90']
@@ -41,13 +40,7 @@ def d4_out_hw(h, w, op):
 
 
 def _check(t, what):
-    _require_cuda(t, what)
-    if oplib.tracing():
-        raise HipPathError(f'{what}: not traceable (a traced TestTimeAugmentation holds the reference\'s aten ops)')
-    if t.dim() != 4:
-        raise HipPathError(f'{what}: a 4-D [N, C, H, W] tensor is required, got {tuple(t.shape)}')
-    if _is_packed(t):
-        raise HipPathError(f'{what}: a packed activation (one convolution\'s private operand) cannot be transformed')
+    _check_map(t, what, 4, '4-D [N, C, H, W]', 'a traced TestTimeAugmentation holds the reference\'s aten ops', 'transformed')
 
 
 def _dense(t):
@@ -109,8 +102,7 @@ def d4_mean(terms, ops):
         raise ValueError(f'd4_mean: ops must be 0..7, got {ops}')
     for t in terms:
         _check(t, 'd4_mean')
-    if torch.is_grad_enabled() and any(t.requires_grad for t in terms):
-        raise HipPathError('d4_mean: inference only (call it under torch.no_grad())')
+    _inference_only('d4_mean', *terms)
     first, nhwc = _dense(terms[0])
     n, c = first.shape[0], first.shape[1]
     ho, wo = d4_out_hw(first.shape[2], first.shape[3], ops[0])
@@ -119,7 +111,7 @@ def d4_mean(terms, ops):
         if tuple(t.shape) != (n, c) + d4_out_hw(ho, wo, o):
             raise ValueError(f'd4_mean: a term of shape {tuple(t.shape)} under op {o} does not give {(n, c, ho, wo)}')
         if nhwc:
-            t = t if is_nhwc(t) else t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+            t = t if is_nhwc(t) else nhwc_copy(t)
         else:
             t = t.contiguous()
         ts.append(t)

@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..hip._base import nhwc_copy
 from . import thcomm
 
 __all__ = ['THRandomRotate90k', 'THRandomHorizontalFlip', 'THRandomVerticalFlip', 'THRandomCrop', 'THRandomScale',
@@ -170,7 +171,7 @@ class THBatchAugment(nn.Module):
             mouts.append(mask)
         out = torch.stack(outs)
         if self.channels_last:
-            out = out.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+            out = nhwc_copy(out)
         if masks is None:
             return out, None
         mout = torch.stack(mouts)

@@ -176,6 +176,25 @@ def test_forced_cases_reach_their_kernel():
     assert lib.evk_d4_force_kernel(-1) == -1
 
 
+def test_d4_and_augment_tile_kernels_share_one_tile_plan():
+    """both families' tile kernels, forced, under a swap op on an NHWC map of every pixel width the tile holds: the same tile
+    edge, row stride and per-thread count (csrc/d4_tile.hpp), and augment's LDS larger by exactly its 32 x 33 int64 label tile"""
+    lib = _lib()
+    aug = (ctypes.c_int32 * 6)()
+    d4_before, aug_before = lib.evk_d4_force_kernel(tc.TILE), lib.evk_augment_force_kernel(1)
+    try:
+        for c in range(1, 65):
+            kernel, tile, tile_cols, stride, lds, per = tc.plan(lib, 1, 40, 24, c, 3)
+            assert lib.evk_augment_plan(40, 24, c, 3, 0, 0, 16, 16, 32, 32, 0, 0, aug) == 0, (c, lib.evk_last_error())
+            assert kernel == tc.TILE and aug[0] == 1, (c, kernel, aug[0])
+            assert (tile, tile_cols, stride, per) == (aug[1], aug[1], aug[2], aug[4]), (c, (tile, stride, per), tuple(aug))
+            assert aug[3] - lds == 32 * 33 * 8, (c, lds, aug[3])
+    finally:
+        lib.evk_d4_force_kernel(d4_before)
+        lib.evk_augment_force_kernel(aug_before)
+    assert lib.evk_d4_force_kernel(-1) == -1 and lib.evk_augment_force_kernel(-1) == -1
+
+
 def test_every_merge_case_lands_on_the_kernel_it_names():
     lib = _lib()
     for case in tc.MERGE_CASES:
