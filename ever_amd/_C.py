@@ -162,6 +162,9 @@ SIGNATURES = {
     'evk_relation_fwd': (c_int, [P, P, P, P, P, c_i32, c_i32, c_i32, P]),
     'evk_relation_workspace_bytes': (c_size_t, [c_i32, c_i32, c_i32]),
     'evk_relation_bwd': (c_int, [P, P, P, P, P, P, P, P, c_i32, c_i32, c_i32, P, c_size_t, P]),
+    'evk_relation_scene_fwd': (c_int, [P, P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_relation_scene_bwd_workspace_bytes': (c_size_t, [c_i32, c_i32, c_i32, c_i32]),
+    'evk_relation_scene_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_i32, c_i32, c_i32, c_i32, P, c_size_t, P]),
     'evk_mean4_fwd': (c_int, [P, P, P, P, P, c_i64, P, P]),
     'evk_loss_stats_doubles': (c_i64, [c_i32]),
     'evk_bce_fwd': (c_int, [P, P, c_i64, c_i64, c_f32, P, P, P]),

@@ -31,6 +31,7 @@
 // Row decode, K cursor and gather are igemm_tile.hpp's, shared with the split kernels; host side and C ABI: conv_igemm.hip.
 #include "conv_route.hpp"
 #include "igemm_tile.hpp"
+#include "smallm_body.hpp"
 
 namespace evk {
 
@@ -183,40 +184,11 @@ static int launch_cfg(IGemmArgs& a, hipStream_t stream) {   // (no statistics ep
 // 2048; reference fs_relation.py:23-29).  An MFMA tile would be >90 % padding and latency bound on a
 // 64-step K loop in 2-4 workgroups; here one workgroup owns one output column and all rows, streams
 // its weight row once with 16-byte loads and reduces across the block.
-constexpr int kSmallM = 32;
 __global__ __launch_bounds__(256) void conv1x1_smallm_kernel(const float* __restrict__ src,
                                                              const float* __restrict__ wgt,
                                                              const float* __restrict__ bias, float* __restrict__ dst,
                                                              int M, int K, int Cd, int relu) {
-  __shared__ float red[4][kSmallM];
-  const int n = blockIdx.x;
-  const int k4 = K >> 2;
-  float acc[kSmallM];
-#pragma unroll
-  for (int m = 0; m < kSmallM; ++m) acc[m] = 0.f;
-  for (int kc = threadIdx.x; kc < k4; kc += 256) {
-    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wgt + (size_t)n * K + kc * 4);
-#pragma unroll
-    for (int m = 0; m < kSmallM; ++m)
-      if (m < M) {
-        const f32x4 x4 = *reinterpret_cast<const f32x4*>(src + (size_t)m * K + kc * 4);
-        acc[m] += w4.x * x4.x + w4.y * x4.y + w4.z * x4.z + w4.w * x4.w;
-      }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int m = 0; m < kSmallM; ++m) {
-    const float s = wave_sum(acc[m]);
-    if (lane == 0) red[wave][m] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < M) {
-    const int m = threadIdx.x;
-    float v = (red[0][m] + red[1][m]) + (red[2][m] + red[3][m]);
-    if (bias) v += bias[n];
-    if (relu) v = fmaxf(v, 0.f);
-    dst[(size_t)m * Cd + n] = v;
-  }
+  smallm_column(src, wgt, bias, dst, M, K, Cd, relu, blockIdx.x);   // (smallm_body.hpp: shared with relation_scene.hip)
 }
 
 static int check_fp32_sizes(const IGemmArgs& a) {

@@ -9,7 +9,7 @@ The wrappers live in one module per kernel family (round 6: this file used to ho
   streams.py     weight gradients on a second stream, the head's branch stream
   conv.py        convolution forward / data gradient / weight gradient, fork nodes, gradient slots, transposed, stem
   norm.py        BatchNorm (+ residual, ReLU), the stem's BatchNorm + ReLU + max-pool
-  pointwise.py   ReLU, add, pools, resampling, global average pool, FS-Relation, BatchNorm + ReLU + classifier dot, mean
+  pointwise.py   ReLU, add, pools, resampling, global average pool, FS-Relation and its scene MLPs, BatchNorm + ReLU + classifier dot, mean
   losses.py      BCE / dice / CE / soft-CE / tversky / focal / per-pixel CE / OHEM / confusion matrix
   depthwise.py   depthwise convolution (groups == channels), the broadcast of a 1x1 map
   hr.py          HRNet: the multi-resolution exchange as one node, bilinear up-sampling into a concat buffer
@@ -33,7 +33,7 @@ from . import _base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse
 
 __all__ = [
     'HipPathError', 'empty_nhwc', 'as_nhwc', 'is_nhwc', 'image_to_nhwc', 'conv2d', 'conv2d_fork', 'conv_transpose2d', 'batch_norm_act', 'relu',
-    'max_pool3x3s2', 'upsample_nearest2x_add', 'upsample_bilinear', 'global_avg_pool', 'fs_relation',
+    'max_pool3x3s2', 'upsample_nearest2x_add', 'upsample_bilinear', 'global_avg_pool', 'fs_relation', 'scene_mlp',
     'mean4', 'add', 'bce_with_logits', 'dice_loss_with_logits', 'cross_entropy', 'soft_cross_entropy',
     'depthwise_conv2d', 'broadcast_hw', 'hr_fuse', 'bilinear_concat', 'd4', 'd4_mean', 'weighted_fuse', 'upsample_nearest2x',
     'd4_compose', 'augment_batch', 'layer_norm', 'scale_residual', 'drop_path_scale', 'attention',

@@ -264,6 +264,76 @@ def fs_relation(scene, content, feat):
     return _inherit_amax(_RelationFn.apply(scene, content, feat), feat)   # sigmoid(.) * feat
 
 
+def _scene_ptrs(ts):
+    """host array of the tensors' device pointers (evk_relation_scene_*: read at the call, nothing goes to the device)"""
+    return (ctypes.c_void_p * len(ts))(*[_ptr(t) for t in ts])
+
+
+def _grad_of_1x1(w):
+    """an uninitialised gradient of the 1x1 weight w over dense [O][I] memory, with exactly w's strides where w is dense
+    (the size-1 dims make the stride tuple ambiguous: AccumulateGrad and the FlatGradDDP bucket views then alias, not copy)"""
+    if w.stride(0) == w.shape[1] and w.stride(1) == 1:
+        return torch.empty_strided(w.shape, w.stride(), device=w.device, dtype=torch.float32)
+    return torch.empty_like(w, memory_format=torch.channels_last)
+
+
+class _SceneMlpFn(Function):
+    """The L scene encoders Conv2d(K, C, 1) -> ReLU -> Conv2d(C, C, 1) of FS-Relation on the pooled vector as ONE node: two
+    launches forward, three backward (include/ever_hip.h: evk_relation_scene_*), all on the caller's stream — the weight
+    gradients are a few microseconds, there is nothing for the side stream to take.  params = (w1, b1, w2, b2) per level."""
+
+    @staticmethod
+    def forward(ctx, s, *params):
+        levels = len(params) // 4
+        n, k, c = s.shape[0], s.shape[1], params[0].shape[0]
+        dev = s.device
+        h = torch.empty((levels, n, c), device=dev, dtype=torch.float32)
+        o = torch.empty((levels, n, c), device=dev, dtype=torch.float32)
+        w1, b1, w2, b2 = (params[i::4] for i in range(4))
+        _C.call('evk_relation_scene_fwd', s.data_ptr(), _scene_ptrs(w1), _scene_ptrs(b1), _scene_ptrs(w2), _scene_ptrs(b2),
+                h.data_ptr(), o.data_ptr(), levels, n, k, c, _stream())
+        _note_param_use(*params)
+        ctx.set_materialize_grads(False)      # (an output nobody used arrives as None = a null pointer = zeros in the kernels)
+        ctx.dims = (levels, n, k, c)
+        ctx.save_for_backward(s, h, *params)
+        return tuple(o[l].view(n, 1, 1, c).permute(0, 3, 1, 2) for l in range(levels))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gs):
+        s, h, *params = ctx.saved_tensors
+        levels, n, k, c = ctx.dims
+        dev = s.device
+        gs = [None if g is None else as_nhwc(g, 'scene_mlp.backward') for g in gs]
+        w1, w2 = params[0::4], params[2::4]
+        dh = torch.empty_like(h)
+        ds = empty_nhwc(n, k, 1, 1, dev)
+        grads = [_grad_of_1x1(p) if p.dim() == 4 else torch.empty_like(p) for p in params]
+        ws_bytes = _C.load().evk_relation_scene_bwd_workspace_bytes(levels, n, k, c)
+        ws = workspace(dev, ws_bytes)
+        _C.call('evk_relation_scene_bwd', s.data_ptr(), h.data_ptr(), _scene_ptrs(gs), _scene_ptrs(w1), _scene_ptrs(w2),
+                dh.data_ptr(), ds.data_ptr(), _scene_ptrs(grads[0::4]), _scene_ptrs(grads[1::4]), _scene_ptrs(grads[2::4]),
+                _scene_ptrs(grads[3::4]), levels, n, k, c, ws.data_ptr(), ws_bytes, _stream())
+        return (ds, *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[1:])])
+
+
+def scene_mlp_admits(levels, n, k, c):
+    """the shapes evk_relation_scene_* take (csrc/relation_scene.hip: scene_shape_ok)"""
+    return 1 <= levels <= 8 and 1 <= n <= 32 and k > 0 and c > 0 and k % 4 == 0 and c % 4 == 0 and levels * c * max(k, c) < 2 ** 31 - 1
+
+
+def scene_mlp(scene, mlps):
+    """[mlp(scene) for mlp in mlps] for scene encoders `Conv2d(K, C, 1) -> ReLU -> Conv2d(C, C, 1)` (reference
+    fs_relation.py:23-29,56-60) as one autograd node (see _SceneMlpFn): a tuple of [N, C, 1, 1] views of one allocation.
+    The caller has checked the modules (module/fs_relation.py) and the shape (scene_mlp_admits)."""
+    _require_cuda(scene, 'scene_mlp')
+    scene = as_nhwc(scene, 'scene_mlp')
+    params = []
+    for m in mlps:
+        params += [m[0].weight, m[0].bias, m[2].weight, m[2].bias]
+    return _SceneMlpFn.apply(scene, *params)
+
+
 class _RelationBnFn(Function):
     """FS-Relation on the two convolution outputs directly: BatchNorm (batch statistics from the convolutions' epilogue
     records) + ReLU of both branches happen inside the relation kernels (include/ever_hip.h: evk_relation_bn_*), their

@@ -4,10 +4,12 @@ scene embedding = GAP(c5) -> per-scale 2-layer 1x1 MLP (bias, ReLU between);
 content / re-encode = 1x1 conv (bias) -> BN -> ReLU on each pyramid level;
 relation r = sigmoid(<scene, content>_channels);  output = r * re-encoded feature  (one fused kernel).
 """
+import torch
 import torch.nn as nn
 
 from ..core import registry
 from ..hip import functional as HF
+from ..hip import oplib
 from ..interface import ERModule
 from .fpn import FPN, AssymetricDecoder
 from .layers import BatchNorm2d, Conv2d, Dropout2d, GroupNorm, HipSequential, ReLU
@@ -32,6 +34,42 @@ def _fusable_bn(seq):
     if not (_takes_epilogue_stats(bn) and bn.training and bn.momentum is not None):
         return False
     return not any(m._forward_hooks or m._forward_pre_hooks for m in (seq, seq[0], bn, seq[2]))
+
+
+def _watched(m):
+    return bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks)
+
+
+def _plain_scene_mlp(enc, cin):
+    """`enc` is exactly what _mlp builds for `cin` input channels — HipSequential(Conv2d 1x1 with bias, ReLU, Conv2d 1x1 with
+    bias), plain strides, dense weights — and nothing watches it"""
+    if type(enc) is not HipSequential or len(enc) != 3 or _watched(enc):
+        return False
+    a, act, b = enc[0], enc[1], enc[2]
+    if type(a) is not Conv2d or type(act) is not ReLU or type(b) is not Conv2d or _watched(a) or _watched(act) or _watched(b):
+        return False
+    for conv, ci in ((a, cin), (b, a.out_channels)):
+        if (conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.padding != (0, 0) or conv.dilation != (1, 1)
+                or conv.groups != 1 or conv.bias is None or conv.in_channels != ci or conv.out_channels != a.out_channels
+                or not HF.is_nhwc(conv.weight) or conv.weight.dtype != torch.float32 or not conv.weight.is_cuda):
+            return False
+    return True
+
+
+def _scene_embeddings(encoders, scene_feature):
+    """[enc(scene_feature) for enc in encoders].  Training, plain MLPs on a pooled [N, K, 1, 1] vector of at most 32 images:
+    all of them as one node of five launches per step (HF.scene_mlp); EVK_SCENE_MLP=0, eval / no-grad, hooks, observers,
+    foreign stacks (FSRelationV2's GroupNorm MLP) or other shapes run the layers as they are."""
+    import os
+    s = scene_feature
+    if (os.environ.get('EVK_SCENE_MLP', '1') != '0' and torch.is_grad_enabled() and s.requires_grad and s.is_cuda
+            and s.dtype == torch.float32 and s.dim() == 4 and s.shape[2:] == (1, 1) and not HF.observers_active()
+            and not oplib.tracing() and len(encoders) > 0
+            and all(enc.training and _plain_scene_mlp(enc, s.shape[1]) for enc in encoders)
+            and len({enc[0].out_channels for enc in encoders}) == 1
+            and HF.scene_mlp_admits(len(encoders), s.shape[0], s.shape[1], encoders[0][0].out_channels)):
+        return list(HF.scene_mlp(s, encoders))
+    return [enc(s) for enc in encoders]
 
 
 class _NoBranches:
@@ -124,9 +162,9 @@ class FSRelation(nn.Module):
         """branches: a HF.HeadBranches session of the calling head (levels 1.. then run on its branch stream and the CALLER
         joins it in front of the first consumer of all levels); None = plain order on the current stream"""
         if self.scale_aware_proj:
-            scenes = [enc(scene_feature) for enc in self.scene_encoder]
+            scenes = _scene_embeddings(list(self.scene_encoder), scene_feature)
         else:
-            scenes = [self.scene_encoder(scene_feature)] * len(features)
+            scenes = _scene_embeddings([self.scene_encoder], scene_feature) * len(features)
         return _relation_levels(self.content_encoders, self.feature_reencoders, scenes, features, branches)
 
 

@@ -660,6 +660,24 @@ int evk_relation_bwd(const float* dout, const float* scene, const float* content
                      const float* r, float* dscene, float* dcontent, float* dfeat, int32_t N,
                      int32_t HW, int32_t C, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The scene branch of FS-Relation — fs_relation.py:23-29,56-60: L scene encoders Conv2d(K, C, 1) -> ReLU -> Conv2d(C, C, 1)
+ * (both with bias) on the pooled vector s [N][K], all levels in two launches forward and three backward, fp32, no atomics,
+ * one fixed summation order (csrc/relation_scene.hip).  w1[l]: [C][K], w2[l]: [C][C], b1[l], b2[l]: [C] — HOST arrays of L
+ * device pointers, the modules' own parameters; they travel in the kernel arguments (nothing is copied to the device, the
+ * calls are capture-safe).  h, o, dh: [L][N][C].  The forward gives the bits of evk_conv2d_fwd on the same [N, K, 1, 1] input.
+ * Backward: g[l] [N][C] = gradient of o[l] (a null entry counts as zeros) -> dh (gradient in front of the ReLU: zero where
+ * h == 0), ds [N][K], dw1[l], db1[l], dw2[l], db2[l] in the parameters' layouts; workspace from
+ * evk_relation_scene_bwd_workspace_bytes (the slice partials of ds).  L <= 8, N <= 32, K % 4 == 0, C % 4 == 0 and biases
+ * present, else EVK_E_UNSUPPORTED; pointers 16-byte aligned, else EVK_E_INVALID; both before any launch. */
+int evk_relation_scene_fwd(const float* s, const float* const* w1, const float* const* b1, const float* const* w2,
+                           const float* const* b2, float* h, float* o, int32_t L, int32_t N, int32_t K, int32_t C,
+                           void* stream);
+size_t evk_relation_scene_bwd_workspace_bytes(int32_t L, int32_t N, int32_t K, int32_t C);
+int evk_relation_scene_bwd(const float* s, const float* h, const float* const* g, const float* const* w1,
+                           const float* const* w2, float* dh, float* ds, float* const* dw1, float* const* db1,
+                           float* const* dw2, float* const* db2, int32_t L, int32_t N, int32_t K, int32_t C,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* `sum(list)/len(list)` over 4 decoder branches — fpn.py:189. */
 int evk_mean4_fwd(const float* a, const float* b, const float* c, const float* d, float* out,
                   int64_t n, uint32_t* out_absmax, void* stream);
