@@ -154,6 +154,8 @@ SIGNATURES = {
     'evk_augment_batch': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P, P, c_i32, c_i32, c_i32, c_i32, P, P, P]),
     'evk_augment_plan': (c_int, [c_i32] * 12 + [C.POINTER(c_i32)]),
     'evk_augment_force_kernel': (c_int, [c_i32]),
+    'evk_augment_scale_batch': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P, P, c_i32, c_i32, c_i32, c_i32, P, P, P]),
+    'evk_augment_scale_plan': (c_int, [c_i32] * 15 + [C.POINTER(c_i32)]),
     'evk_stitch_add': (c_int, [P, P, c_i32, P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_stitch_finalize': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P, c_i32, c_f32, c_i32, P]),
     'evk_stitch_plan': (c_int, [P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),

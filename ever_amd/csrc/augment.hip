@@ -26,6 +26,8 @@
 // (mod 32) puts them on consecutive banks for every C.  Both are derived, not measured.  The label tile is T x (T + 1) int64.
 // Sources are read a byte (uint8) or a word (fp32) at a time: there is no wide-load path, so no alignment is assumed.
 // Indices are 32-bit: the entry point refuses a sample or an output of 2^31 elements or more.
+// The scaled pass (evk_augment_scale_batch, THRandomScale in front of the chain) is a kernel of its own further down.
+#include <string.h>
 #include <atomic>
 #include "d4_tile.hpp"
 
@@ -303,6 +305,195 @@ __global__ __launch_bounds__(256) void augment_tile_kernel(const long long* __re
   }
 }
 
+// ---- the scaled pass (evk_augment_scale_batch): THRandomScale in front of the chain.  T = d4(Z, op) with Z [Hz, Wz, C] the
+// bilinear (align_corners) image of S and the nearest image of its label map, neither of which is ever stored: an output pixel
+// decodes its Z pixel (d4_source), from it four clamped source pixels and four weights, and its label's source pixel, ONCE,
+// and its C channels share them.  So a thread owns whole pixels: four consecutive ones with 16-byte stores (NCHW: one store
+// per channel; NHWC: their 4 C consecutive floats as C stores), else one.  Taps are byte or dword loads at any address; the
+// four taps of neighbouring lanes share cache lines and there is no LDS form.  The transposing ops pay for that: measured on
+// an MI355X at 191-197 us against 42-50 us for the others (16 x 1024^2 x 3 -> 16 x 3 x 512^2, f = 1.25; table in DESIGN 2.16).
+// Records are kAugScaleRecWords int64: the eight above, then Hz, Wz, the bit image of s = float(1 / f), 0.
+constexpr int kAugScaleRecWords = 12;
+
+struct AugScaleRec {
+  AugRec r;
+  int Hz, Wz;
+  float s, ry, rx;
+  bool scaled;      // false: Hz == Hs, Wz == Ws, s == 1: Z is S itself, one tap
+};
+__host__ __device__ __forceinline__ float aug_scale_ratio(int src, int dst) {
+  if (dst <= 1) return 0.0f;      // one correctly rounded division on either side
+#ifdef __HIP_DEVICE_COMPILE__
+  return __fdiv_rn((float)(src - 1), (float)(dst - 1));
+#else
+  return (float)(src - 1) / (float)(dst - 1);
+#endif
+}
+__device__ __forceinline__ AugScaleRec aug_scale_rec(const long long* __restrict__ table, int n) {
+  const long long* t = table + (size_t)n * kAugScaleRecWords;
+  AugScaleRec q;
+  q.r.img = reinterpret_cast<const uint8_t*>(t[0]);
+  q.r.mask = reinterpret_cast<const uint8_t*>(t[1]);
+  q.r.Hs = (int)t[2]; q.r.Ws = (int)t[3]; q.r.op = (int)t[4]; q.r.y0 = (int)t[5]; q.r.x0 = (int)t[6];
+  q.Hz = (int)t[8]; q.Wz = (int)t[9];
+  q.s = __uint_as_float((uint32_t)t[10]);
+  q.ry = aug_scale_ratio(q.r.Hs, q.Hz);
+  q.rx = aug_scale_ratio(q.r.Ws, q.Wz);
+  q.scaled = !(q.Hz == q.r.Hs && q.Wz == q.r.Ws && q.s == 1.0f);
+  return q;
+}
+
+// What the C channels of one output pixel share.  kind 0: outside the window (+0.0f, the pad label); 1: inside the window, past
+// T (raw 0, label 0); 2: one tap at o00 (an unscaled sample); 3: four taps.  Offsets are in source pixels.
+struct AugScalePix {
+  int kind;
+  uint32_t o00, o01, o10, o11, lab;
+  float hy, ly, hx, lx;
+};
+// Every operation of the contract is rounded on its own.  The compiler contracts a * b + c into one fma by default, and the
+// __fmul_rn / __fadd_rn intrinsics do not stop it (they are plain operators that inherit the default), so the sums below are
+// written under `fp contract(off)`: an addition compiled there carries no permission to fuse.
+// one axis: the first tap, whether a second one follows it, and the weights
+__device__ __forceinline__ void aug_scale_axis(float ratio, int z, int n, int& i0, int& step, float& lo, float& hi) {
+#pragma clang fp contract(off)
+  const float pos = ratio * (float)z;
+  i0 = min((int)pos, n - 1);
+  step = i0 < n - 1;
+  lo = pos - (float)i0;
+  hi = 1.0f - lo;
+}
+__device__ __forceinline__ AugScalePix aug_scale_pixel(const AugScaleRec& q, const AugGeom& g, int r, int c) {
+  AugScalePix p = {};
+  if (r >= g.ch || c >= g.cw) return p;
+  const int op = q.r.op;
+  const int Ht = (op & 1) ? q.Wz : q.Hz, Wt = (op & 1) ? q.Hz : q.Wz;
+  const int a = q.r.y0 + r, b = q.r.x0 + c;
+  p.kind = 1;
+  if (a >= Ht || b >= Wt) return p;
+  int za, zb;
+  d4_source(op, a, b, Ht, Wt, za, zb);
+  const int Hs = q.r.Hs, Ws = q.r.Ws;
+  if (!q.scaled) {
+    p.kind = 2;
+    p.o00 = p.lab = (uint32_t)za * Ws + zb;
+    return p;
+  }
+  p.kind = 3;
+  int y0, ys, x0, xs;
+  aug_scale_axis(q.ry, za, Hs, y0, ys, p.ly, p.hy);
+  aug_scale_axis(q.rx, zb, Ws, x0, xs, p.lx, p.hx);
+  p.o00 = (uint32_t)y0 * Ws + x0;
+  p.o01 = p.o00 + xs;
+  p.o10 = p.o00 + (ys ? Ws : 0);
+  p.o11 = p.o10 + xs;
+  // a >= 0 and s > 0: the truncation is floorf; a product past the int range saturates and the clamp takes it
+  const int my = min((int)((float)za * q.s), Hs - 1), mx = min((int)((float)zb * q.s), Ws - 1);
+  p.lab = (uint32_t)my * Ws + mx;
+  return p;
+}
+__device__ __forceinline__ float aug_scale_value(const AugScaleRec& q, const AugGeom& g, const float* __restrict__ mean,
+                                                 const float* __restrict__ stdv, const AugScalePix& p, int k) {
+#pragma clang fp contract(off)
+  if (p.kind == 0) return 0.0f;
+  float raw = 0.0f;
+  if (p.kind == 2) raw = aug_load_raw(q.r, g, p.o00 * g.C + k);
+  if (p.kind == 3) {
+    const float p00 = aug_load_raw(q.r, g, p.o00 * g.C + k), p01 = aug_load_raw(q.r, g, p.o01 * g.C + k);
+    const float p10 = aug_load_raw(q.r, g, p.o10 * g.C + k), p11 = aug_load_raw(q.r, g, p.o11 * g.C + k);
+    const float top = p.hx * p00 + p.lx * p01;
+    const float bot = p.hx * p10 + p.lx * p11;
+    raw = p.hy * top + p.ly * bot;
+  }
+  return aug_normalize(raw, mean, stdv, k);
+}
+__device__ __forceinline__ long long aug_scale_label(const AugScaleRec& q, const AugGeom& g, const AugScalePix& p) {
+  return p.kind == 0 ? g.mask_pad : p.kind == 1 ? 0 : aug_load_label(q.r, g, p.lab);
+}
+// PIX = 4: four consecutive output pixels per thread and 16-byte stores (Ho*Wo a multiple of 4, outputs on the 16-byte grid);
+// PIX = 1: a pixel per thread, 4-byte stores, any size and address.
+template <int PIX>
+__global__ __launch_bounds__(256) void augment_scale_kernel(const long long* __restrict__ table, const float* __restrict__ mean,
+                                                            const float* __restrict__ stdv, float* __restrict__ out,
+                                                            void* __restrict__ out_mask, const AugGeom g) {
+  const int n = blockIdx.y;
+  const uint32_t HW = g.fHW.div, pix = (blockIdx.x * 256u + threadIdx.x) * PIX;
+  if (pix >= HW) return;
+  const AugScaleRec q = aug_scale_rec(table, n);
+  uint32_t r = fdiv(pix, g.fWo), c = pix - r * g.Wo;
+  AugScalePix p[PIX];
+#pragma unroll
+  for (int i = 0; i < PIX; ++i) {
+    p[i] = aug_scale_pixel(q, g, (int)r, (int)c);
+    if (++c == (uint32_t)g.Wo) { c = 0; ++r; }
+  }
+  const uint32_t C = g.C;
+  if constexpr (PIX == 1) {
+    for (uint32_t k = 0; k < C; ++k)
+      out[g.nchw ? ((uint32_t)n * C + k) * HW + pix : ((uint32_t)n * HW + pix) * C + k] = aug_scale_value(q, g, mean, stdv, p[0], k);
+    if (g.mask_mode != kAugNoMask) store_label(out_mask, aug_labels_i64(g), (uint32_t)n * HW + pix, aug_scale_label(q, g, p[0]));
+  } else {
+    if (g.nchw) {
+      for (uint32_t k = 0; k < C; ++k) {
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = aug_scale_value(q, g, mean, stdv, p[i], k);
+        *reinterpret_cast<f32x4*>(out + ((size_t)n * C + k) * HW + pix) = f32x4{v[0], v[1], v[2], v[3]};
+      }
+    } else {
+      float* o = out + ((size_t)n * HW + pix) * C;      // 4 C floats from a multiple of 4 C: on the 16-byte grid
+      // pixel-major, so each pixel's registers are named at compile time; element m goes to slot m % 4 of the pending store by
+      // selects (an indexed array would go to scratch), and m is the same in every lane: the store is uniform
+      float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
+      uint32_t m = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        for (uint32_t k = 0; k < C; ++k, ++m) {
+          const float val = aug_scale_value(q, g, mean, stdv, p[i], k);
+          const uint32_t slot = m & 3u;
+          if (slot == 3u) reinterpret_cast<f32x4*>(o)[m >> 2] = f32x4{v0, v1, v2, val};
+          v0 = slot == 0u ? val : v0;
+          v1 = slot == 1u ? val : v1;
+          v2 = slot == 2u ? val : v2;
+        }
+      }
+    }
+    if (g.mask_mode != kAugNoMask) {
+      long long l[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) l[i] = aug_scale_label(q, g, p[i]);
+      store_labels4(out_mask, aug_labels_i64(g), (size_t)n * HW + pix, l);
+    }
+  }
+}
+
+// One sample of the scaled pass against the launch: every refusal that concerns a sample.  Host arithmetic only.
+static int aug_scale_plan(int Hs, int Ws, int C, int op, int y0, int x0, int ch, int cw, int Ho, int Wo, int Hz, int Wz,
+                          uint32_t s_bits, AugPlan* pl) {
+  EVK_REQUIRE(Hs > 0 && Ws > 0 && C > 0 && ch > 0 && cw > 0 && Ho > 0 && Wo > 0 && op >= 0 && op <= 7, EVK_E_INVALID,
+              "augment_scale: bad argument (non-positive size or op outside 0..7)");
+  EVK_REQUIRE(C <= kTileMaxC, EVK_E_UNSUPPORTED, "augment_scale: %d channels (up to %d are implemented)", C, kTileMaxC);
+  EVK_REQUIRE(ch <= Ho && cw <= Wo, EVK_E_INVALID, "augment_scale: crop %d x %d is larger than the output %d x %d", ch, cw, Ho, Wo);
+  const int64_t nsrc = (int64_t)Hs * Ws * C;
+  EVK_REQUIRE(nsrc < 0x80000000LL, EVK_E_UNSUPPORTED, "augment_scale: a source of %lld elements (fewer than 2^31 are implemented)",
+              (long long)nsrc);
+  EVK_REQUIRE(Hz >= 1 && Wz >= 1, EVK_E_INVALID, "augment_scale: scaled size %d x %d", Hz, Wz);
+  const int64_t nz = (int64_t)Hz * Wz * C;
+  EVK_REQUIRE(nz < 0x80000000LL, EVK_E_UNSUPPORTED, "augment_scale: a scaled image of %lld elements (fewer than 2^31 are implemented)",
+              (long long)nz);
+  // finite and positive: sign 0, exponent not all ones, not zero
+  EVK_REQUIRE(s_bits != 0 && s_bits < 0x7f800000u, EVK_E_INVALID, "augment_scale: 1 / factor (bits 0x%08x) is not finite and positive",
+              s_bits);
+  const bool swap = op & 1;
+  const int Ht = swap ? Wz : Hz, Wt = swap ? Hz : Wz;
+  const int ymax = (Ht > ch ? Ht : ch) - ch, xmax = (Wt > cw ? Wt : cw) - cw;
+  EVK_REQUIRE(y0 >= 0 && y0 <= ymax && x0 >= 0 && x0 <= xmax, EVK_E_INVALID,
+              "augment_scale: crop origin (%d, %d) outside [0, %d] x [0, %d]", y0, x0, ymax, xmax);
+  *pl = AugPlan{};
+  pl->kernel = kAugDirect;
+  pl->vec = g_aug_force.load(std::memory_order_relaxed) != 2 && ((int64_t)Ho * Wo) % 4 == 0;
+  return EVK_OK;
+}
+
 }  // namespace evk
 
 using namespace evk;
@@ -378,4 +569,63 @@ extern "C" int evk_augment_batch(const int64_t* records, const int64_t* table, i
     }
   }
   return check_launch("augment_batch");
+}
+
+extern "C" int evk_augment_scale_plan(int32_t Hs, int32_t Ws, int32_t C, int32_t op, int32_t y0, int32_t x0, int32_t crop_h,
+                                      int32_t crop_w, int32_t Ho, int32_t Wo, int32_t src_f32, int32_t nchw, int32_t Hz, int32_t Wz,
+                                      int32_t s_bits, int32_t* out) {
+  EVK_REQUIRE(out, EVK_E_INVALID, "augment_scale_plan: out is a null pointer");
+  (void)src_f32; (void)nchw;      // one kernel form for every source type and layout
+  AugPlan pl;
+  const int rc = aug_scale_plan(Hs, Ws, C, op, y0, x0, crop_h, crop_w, Ho, Wo, Hz, Wz, (uint32_t)s_bits, &pl);
+  if (rc != EVK_OK) return rc;
+  const float ry = aug_scale_ratio(Hs, Hz), rx = aug_scale_ratio(Ws, Wz);
+  out[0] = pl.kernel; out[1] = (pl.vec ? 4 : 1) * C; out[2] = pl.vec;
+  memcpy(&out[3], &ry, sizeof(float));
+  memcpy(&out[4], &rx, sizeof(float));
+  return EVK_OK;
+}
+
+extern "C" int evk_augment_scale_batch(const int64_t* records, const int64_t* table, int32_t N, int32_t C, int32_t crop_h,
+                                       int32_t crop_w, int32_t Ho, int32_t Wo, const float* mean, const float* stdv,
+                                       int32_t mask_pad_value, int32_t nchw, int32_t src_f32, int32_t mask_mode, float* out,
+                                       void* out_mask, void* stream) {
+  EVK_REQUIRE(records && table, EVK_E_INVALID, "augment_scale_batch: null record table");
+  EVK_REQUIRE(out && N > 0, EVK_E_INVALID, "augment_scale_batch: bad argument (null output or non-positive batch)");
+  EVK_REQUIRE((mean == nullptr) == (stdv == nullptr), EVK_E_INVALID, "augment_scale_batch: mean and std come together or not at all");
+  EVK_REQUIRE(mask_mode >= kAugNoMask && mask_mode <= kAugMaskI64, EVK_E_INVALID, "augment_scale_batch: mask mode %d outside 0..3",
+              mask_mode);
+  EVK_REQUIRE(mask_mode == kAugNoMask || out_mask, EVK_E_INVALID, "augment_scale_batch: a mask mode without a mask output");
+  AugPlan pl;
+  for (int i = 0; i < N; ++i) {
+    const int64_t* r = records + (size_t)i * kAugScaleRecWords;
+    EVK_REQUIRE(r[0] != 0, EVK_E_INVALID, "augment_scale_batch: image %d is a null pointer", i);
+    EVK_REQUIRE(mask_mode == kAugNoMask || r[1] != 0, EVK_E_INVALID, "augment_scale_batch: mask %d is a null pointer", i);
+    for (int k = 2; k < 10; ++k)
+      EVK_REQUIRE(k == 7 || (r[k] >= 0 && r[k] < 0x80000000LL), EVK_E_INVALID, "augment_scale_batch: record %d, word %d out of range",
+                  i, k);
+    EVK_REQUIRE(r[10] >= 0 && r[10] <= 0xffffffffLL, EVK_E_INVALID, "augment_scale_batch: record %d, word 10 out of range", i);
+    const int rc = aug_scale_plan((int)r[2], (int)r[3], C, (int)r[4], (int)r[5], (int)r[6], crop_h, crop_w, Ho, Wo, (int)r[8],
+                                  (int)r[9], (uint32_t)r[10], &pl);
+    if (rc != EVK_OK) return rc;
+  }
+  const int64_t total = (int64_t)N * Ho * Wo * C;
+  EVK_REQUIRE(total < 0x80000000LL, EVK_E_UNSUPPORTED,
+              "augment_scale_batch: an output of %lld elements (fewer than 2^31 are implemented)", (long long)total);
+  EVK_REQUIRE(N <= 65535, EVK_E_UNSUPPORTED, "augment_scale_batch: %d samples (up to 65535 per launch)", N);
+  AugGeom g = {};
+  g.ch = crop_h; g.cw = crop_w; g.Ho = Ho; g.Wo = Wo; g.C = C;
+  g.nchw = nchw != 0; g.src_f32 = src_f32 != 0; g.mask_mode = mask_mode; g.mask_pad = mask_pad_value;
+  g.fC = make_fastdiv((uint32_t)C); g.fWo = make_fastdiv((uint32_t)Wo); g.fHW = make_fastdiv((uint32_t)(Ho * Wo));
+  g.fT = g.fTC = g.fTT = g.fTilesC = make_fastdiv(1);
+  hipStream_t st = (hipStream_t)stream;
+  const long long* tab = reinterpret_cast<const long long*>(table);
+  const int64_t hw = (int64_t)Ho * Wo;
+  if (pl.vec && aligned16(out) && (mask_mode == kAugNoMask || aligned16(out_mask)))
+    hipLaunchKernelGGL(augment_scale_kernel<4>, dim3((unsigned)((hw / 4 + 255) / 256), (unsigned)N), dim3(256), 0, st, tab, mean,
+                       stdv, out, out_mask, g);
+  else
+    hipLaunchKernelGGL(augment_scale_kernel<1>, dim3((unsigned)((hw + 255) / 256), (unsigned)N), dim3(256), 0, st, tab, mean, stdv,
+                       out, out_mask, g);
+  return check_launch("augment_scale_batch");
 }

@@ -3,7 +3,8 @@ reference's `np.random` calls in its order (the same seed yields the same parame
 reference does not have: the whole chain for a list of images, on the GPU as ONE kernel launch (hip/augment.py).
 
 The per-image classes evaluate torch expressions on whatever device their tensors are on; they are the compatibility surface,
-not the hot path.  `THRandomScale` stays outside the fused pass: bilinear parity with aten is a different problem."""
+not the hot path.  `THBatchAugment(scale_range=...)` puts `THRandomScale` in front of the chain and inside the fused pass,
+with its arithmetic written out (include/ever_hip.h) and held to aten's within a derived bound, not bit for bit."""
 import math
 
 import numpy as np
@@ -30,6 +31,24 @@ def _draw_k(k):
 def _draw_flip(p):
     """True = flip.  `p < uniform()` means "leave as is", as the reference writes it"""
     return not (p < np.random.uniform())
+
+
+def _scale_factors(scale_range, scale_step):
+    """the reference's list of factors (THRandomScale.__init__)"""
+    return np.linspace(scale_range[0], scale_range[1], int((scale_range[1] - scale_range[0]) / scale_step) + 1)
+
+
+def _draw_scale(factors):
+    return np.random.choice(factors, size=1)[0]
+
+
+def _rescale(images, masks, factor):
+    """THRandomScale's expression at a given factor: (image,) or (image, mask)"""
+    nchw = images.permute(2, 0, 1)[None]
+    out = (F.interpolate(nchw, scale_factor=factor, mode='bilinear', align_corners=True)[0].permute(1, 2, 0),)
+    if masks is not None:
+        out += (F.interpolate(masks[None, None], scale_factor=factor, mode='nearest')[0][0],)
+    return out
 
 
 def _draw_origin(h, w, crop_size):
@@ -100,21 +119,16 @@ class THRandomScale(nn.Module):
 
     def __init__(self, scale_range=(0.5, 2.0), scale_step=0.25):
         super().__init__()
-        factors = np.linspace(scale_range[0], scale_range[1], int((scale_range[1] - scale_range[0]) / scale_step) + 1)
-        self.scale_factor = np.random.choice(factors, size=1)[0]
+        self.scale_factor = _draw_scale(_scale_factors(scale_range, scale_step))
 
     def __call__(self, images, masks=None):
-        nchw = images.permute(2, 0, 1)[None]
-        out = (F.interpolate(nchw, scale_factor=self.scale_factor, mode='bilinear', align_corners=True)[0].permute(1, 2, 0),)
-        if masks is not None:
-            out += (F.interpolate(masks[None, None], scale_factor=self.scale_factor, mode='nearest')[0][0],)
-        return out
+        return _rescale(images, masks, self.scale_factor)
 
 
 class THBatchAugment(nn.Module):
-    """THRandomRotate90k(rotate_k) -> THRandomHorizontalFlip(hflip_p) -> THRandomVerticalFlip(vflip_p) ->
-    THRandomCrop(crop_size) -> THChannelFirst2 -> THMeanStdNormalize2(mean, std) -> THDivisiblePad(size_divisor,
-    mask_pad_value) for every image of a list, then `torch.stack`.
+    """[THRandomScale(scale_range, scale_step) ->] THRandomRotate90k(rotate_k) -> THRandomHorizontalFlip(hflip_p) ->
+    THRandomVerticalFlip(vflip_p) -> THRandomCrop(crop_size) -> THChannelFirst2 -> THMeanStdNormalize2(mean, std) ->
+    THDivisiblePad(size_divisor, mask_pad_value) for every image of a list, then `torch.stack`.
 
     Called with a list of [H, W, C] images (uint8 or fp32, any sizes) and an optional list of [H, W] masks (uint8 or int64).
     For each image in list order it draws k, hflip, vflip, ymin, xmin exactly as that pipeline would when run image by image.
@@ -124,10 +138,24 @@ class THBatchAugment(nn.Module):
     Returns (images, masks or None).  `channels_last=True`: a logical [N, C, Ho, Wo] tensor over NHWC memory, which the
     models take without their boundary transpose; False: the reference's NCHW-contiguous tensor; the values are identical.
     `mask_dtype`: None keeps the masks' dtype, torch.int64 gives the label maps the losses take.  `mean=None` (with
-    `std=None`) only casts to fp32.  `size_divisor=None` leaves the crop size."""
+    `std=None`) only casts to fp32.  `size_divisor=None` leaves the crop size.
+
+    `scale_range=(lo, hi)` adds the rescale step in front: bilinear with align_corners=True for the image, nearest for the
+    mask, by one of the reference's factors `np.linspace(lo, hi, int((hi - lo) / scale_step) + 1)`.  `scale_each=True` draws
+    the factor per image, before that image's k, hflip, vflip, ymin, xmin.  `scale_each=False` draws ONE factor when the
+    object is built, as `THRandomScale` does: under one seed the object then equals the reference pipeline THRandomScale ->
+    THRandomRotate90k -> ... built and then run.  The crop origin is drawn on the rescaled, rotated size.  `scale_range=None`
+    consumes the random stream exactly as without the keyword.
+    The rescale works on the image cast to fp32 first, on both paths: a uint8 image is NOT rounded back to uint8 after the
+    interpolation (aten's CPU kernel would, given a uint8 tensor).  CUDA inputs: still ONE launch, with the arithmetic of
+    include/ever_hip.h (evk_augment_scale_batch), within 8 * 2^-23 * max|image| of aten before normalisation; its labels are
+    `M[min(int(a * float(1 / f)), H - 1), ...]`.  CPU inputs: aten's own `F.interpolate`, whose labels follow a shortcut of
+    aten's where a rescaled side equals the source side or twice it, and which has no nearest kernel for int64: int64 masks
+    need the device path or a uint8 mask (with mask_dtype=torch.int64)."""
 
     def __init__(self, crop_size, size_divisor=None, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), rotate_k=None,
-                 hflip_p=0.5, vflip_p=0.5, mask_pad_value=255, channels_last=True, mask_dtype=None):
+                 hflip_p=0.5, vflip_p=0.5, mask_pad_value=255, channels_last=True, mask_dtype=None, scale_range=None,
+                 scale_step=0.25, scale_each=True):
         super().__init__()
         if (mean is None) != (std is None):
             raise ValueError('THBatchAugment: mean and std come together or not at all')
@@ -138,6 +166,17 @@ class THBatchAugment(nn.Module):
         self.mask_pad_value = mask_pad_value
         self.channels_last = channels_last
         self.mask_dtype = mask_dtype
+        self.scale_factors = None if scale_range is None else _scale_factors(scale_range, scale_step)
+        self.scale_each = bool(scale_each)
+        self.scale_factor = None      # scale_each=False: the one factor, drawn now
+        if self.scale_factors is not None and not self.scale_each:
+            self.scale_factor = _draw_scale(self.scale_factors)
+
+    def _next_scale(self):
+        """the factor of the next image (a draw when scale_each), or None without a scale step"""
+        if self.scale_factors is None:
+            return None
+        return float(_draw_scale(self.scale_factors) if self.scale_each else self.scale_factor)
 
     @property
     def out_size(self):
@@ -159,7 +198,11 @@ class THBatchAugment(nn.Module):
                        THRandomVerticalFlip(self.vflip_p), THRandomCrop(self.crop_size))
         outs, mouts = [], []
         for i, image in enumerate(images):
-            cur = image if masks is None else (image, masks[i])
+            factor = self._next_scale()
+            if factor is None:
+                cur = image if masks is None else (image, masks[i])
+            else:
+                cur = _rescale(image.float(), None if masks is None else masks[i], factor)
             for stage in random_part:
                 cur = stage(*cur) if isinstance(cur, tuple) else stage(cur)
             image, mask = cur[0], (cur[1] if len(cur) > 1 else None)
@@ -180,19 +223,26 @@ class THBatchAugment(nn.Module):
     # ---- one launch: CUDA inputs
     def _fused(self, images, masks):
         from ..hip import functional as HF
-        ops, origins = [], []
+        ops, origins, scales = [], [], []
         for image in images:
+            factor = self._next_scale()
+            h, w = image.shape[0], image.shape[1]
+            if factor is not None:
+                h, w = HF.scaled_hw(h, w, factor)
+                if h < 1 or w < 1:
+                    raise ValueError(f'THBatchAugment: a {image.shape[0]} x {image.shape[1]} image rescaled by {factor} is empty')
+                scales.append(factor)
             k, hflip, vflip = _draw_k(self.rotate_k), _draw_flip(self.hflip_p), _draw_flip(self.vflip_p)
             op = HF.D4_ROT90.get(k, HF.D4_IDENTITY)
             if hflip:
                 op = HF.d4_compose(op, HF.D4_HFLIP)
             if vflip:
                 op = HF.d4_compose(op, HF.D4_VFLIP)
-            ht, wt = HF.d4_out_hw(image.shape[0], image.shape[1], op)
+            ht, wt = HF.d4_out_hw(h, w, op)
             if masks is None and (ht < self.crop_size[0] or wt < self.crop_size[1]):
                 raise TypeError('THBatchAugment: an image smaller than the crop needs its mask (THRandomCrop pads both)')
             ops.append(op)
             origins.append(_draw_origin(ht, wt, self.crop_size))
         return HF.augment_batch(images, masks, ops, origins, self.crop_size, self.out_size, self.mean, self.std,
                                 mask_pad_value=self.mask_pad_value, channels_last=self.channels_last,
-                                mask_dtype=self.mask_dtype)
+                                mask_dtype=self.mask_dtype, scales=scales or None)

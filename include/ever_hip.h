@@ -610,6 +610,39 @@ int evk_augment_plan(int32_t Hs, int32_t Ws, int32_t C, int32_t op, int32_t y0, 
  * on, in this process, the plan names `kernel` (0, 1, or 2: direct with 4-byte stores only) wherever it is legal (1 needs a swap
  * op) and follows its own rule elsewhere; any other value, -1 by custom, restores the rule.  Returns the previous setting. */
 int evk_augment_force_kernel(int32_t kernel);
+/* evk_augment_batch with the reference's THRandomScale (bilinear align_corners=True for the image, nearest for the labels) in
+ * front of the chain, inside the same single launch.  Sample i has a factor f > 0; the CALLER computes the scaled size
+ * Hz = int(floor(double(Hs) * f)), Wz likewise (aten's output sizes) and s = float(1.0 / double(f)).  Z [Hz,Wz,C] is the
+ * scaled image, and everything after Z is evk_augment_batch with Z for S: T = d4(Z, op), the window at (y0, x0) of T, raw 0
+ * and label 0 inside the window where T ends, normalise, pad.
+ * Image, fp32, every operation rounded on its own (no fma):
+ *   ry = Hz > 1 ? float(Hs - 1) / float(Hz - 1) : 0;  sy = ry * float(a);  y0 = min(int(sy), Hs - 1);  y1 = y0 + (y0 < Hs - 1);
+ *   ly = sy - float(y0);  hy = 1 - ly;  the same for x;  p** = float(S[y*, x*, k])
+ *   Z[a,b,k] = hy * (hx * p00 + lx * p01) + ly * (hx * p10 + lx * p11)
+ * A uint8 source is interpolated in fp32 and NOT rounded back to uint8 (aten's CPU kernel rounds back when handed a uint8
+ * tensor): the pass is the chain applied to the image cast to fp32 first.  The min-clamps are there so that no record can
+ * cause a read outside the source; aten has none.
+ * Labels: Zm[a,b] = M[min(int(floorf(float(a) * s)), Hs - 1), min(int(floorf(float(b) * s)), Ws - 1)], for all three mask
+ * modes (aten has no nearest kernel for int64).
+ * A sample with Hz == Hs, Wz == Ws and s == 1.0f is not scaled: Z = S, one tap, the bits of evk_augment_batch (the formula
+ * gives the same bits on finite values, but for the sign of a zero).
+ * Relation to aten (tests/augment_scale_common.py is the definition, aten a second witness): the image is not bit-equal to
+ * aten's CPU bilinear, which evaluates the same weights in another order; both make at most 9 roundings of non-negative
+ * terms, so they differ by at most 8 * 2^-23 * max|source|.  The labels equal aten's CPU nearest wherever Hz is neither Hs nor
+ * 2 Hs and Wz neither Ws nor 2 Ws; there aten takes a same-size / double-size shortcut its generic formula does not reproduce.
+ * Records are 12 int64: { image address, mask address, Hs, Ws, op, y0, x0, 0, Hz, Wz, bit image of s in the low 32 bits, 0 }.
+ * Return codes and refusals as evk_augment_batch, with the origin limits taken on d4 of (Hz, Wz), and further: -1 for Hz < 1,
+ * Wz < 1, s not finite or not positive; -2 for Hz * Wz * C >= 2^31.  Every refusal comes before any launch. */
+int evk_augment_scale_batch(const int64_t* records, const int64_t* table, int32_t N, int32_t C, int32_t crop_h, int32_t crop_w,
+                            int32_t Ho, int32_t Wo, const float* mean, const float* std, int32_t mask_pad_value, int32_t nchw,
+                            int32_t src_f32, int32_t mask_mode, float* out, void* out_mask, void* stream);
+/* Host only, no launch: the checks evk_augment_scale_batch makes on one sample (same return codes).  out[5] = { kernel (0:
+ * the scaled direct kernel, the only form), output elements per thread (4 C with 16-byte stores, else C: a thread owns whole
+ * pixels), 16-byte stores (Ho*Wo % 4 == 0; the launcher falls back for an output off the 16-byte grid), bit image of ry, bit
+ * image of rx }. */
+int evk_augment_scale_plan(int32_t Hs, int32_t Ws, int32_t C, int32_t op, int32_t y0, int32_t x0, int32_t crop_h,
+                           int32_t crop_w, int32_t Ho, int32_t Wo, int32_t src_f32, int32_t nchw, int32_t Hz, int32_t Wz,
+                           int32_t s_bits, int32_t* out);
 
 /* Whole-scene tiled inference, the stitching half (csrc/stitch.hip; magic/bigimage/scene.py) — per window the
  * `out[:, y0:y1, x0:x1] += s; count[y0:y1, x0:x1] += 1` of a sliding-window driver, per scene its `out / count`.
