@@ -159,6 +159,13 @@ SIGNATURES = {
     'evk_stitch_add': (c_int, [P, P, c_i32, P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
     'evk_stitch_finalize': (c_int, [P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P, c_i32, c_f32, c_i32, P]),
     'evk_stitch_plan': (c_int, [P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
+    'evk_ppm_pool_workspace_bytes': (c_size_t, [c_i32, c_i32, c_i32, c_i32, P, c_i32]),
+    'evk_ppm_pool_fwd': (c_int, [P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, P, c_size_t, P]),
+    'evk_ppm_pool_bwd': (c_int, [P, P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_ppm_expand_fwd': (c_int, [P, P, P, c_i32, P, c_i32, c_i32, c_i32, c_i32, c_i32, P]),
+    'evk_ppm_expand_bwd_workspace_bytes': (c_size_t, [c_i32, c_i32, c_i32, c_i32, c_i32, P, c_i32]),
+    'evk_ppm_expand_bwd': (c_int, [P, P, P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P, c_size_t, P]),
+    'evk_ppm_plan': (c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, P, c_i32, C.POINTER(c_i32)]),
     'evk_gap_fwd': (c_int, [P, P, c_i32, c_i32, c_i32, P]),
     'evk_gap_bwd': (c_int, [P, P, c_i32, c_i32, c_i32, P]),
     'evk_relation_fwd': (c_int, [P, P, P, P, P, c_i32, c_i32, c_i32, P]),

@@ -14,6 +14,7 @@ The wrappers live in one module per kernel family (round 6: this file used to ho
   depthwise.py   depthwise convolution (groups == channels), the broadcast of a 1x1 map
   hr.py          HRNet: the multi-resolution exchange as one node, bilinear up-sampling into a concat buffer
   fuse.py        BiFPN: the learned weighted fusion node, nearest x2 as an index shift
+  pyramid.py     pyramid pooling: K adaptive pools from one read, bilinear expand + concat as one write
   transform.py   test-time augmentation: the eight symmetries of the square as one copy, their fused mean
   augment.py     input preparation: dihedral op, crop, normalisation and padding of a whole batch as one launch
   rownorm.py     LayerNorm over the channels of a map or the last axis of a token matrix, the layer-scale residual
@@ -29,7 +30,7 @@ Reference call sites replaced (ever/module/...): see the per-function docstrings
 import sys
 import types
 
-from . import _base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention, stitch
+from . import _base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention, stitch, pyramid
 
 __all__ = [
     'HipPathError', 'empty_nhwc', 'as_nhwc', 'is_nhwc', 'image_to_nhwc', 'conv2d', 'conv2d_fork', 'conv_transpose2d', 'batch_norm_act', 'relu',
@@ -37,10 +38,10 @@ __all__ = [
     'mean4', 'add', 'bce_with_logits', 'dice_loss_with_logits', 'cross_entropy', 'soft_cross_entropy',
     'depthwise_conv2d', 'broadcast_hw', 'hr_fuse', 'bilinear_concat', 'd4', 'd4_mean', 'weighted_fuse', 'upsample_nearest2x',
     'd4_compose', 'augment_batch', 'layer_norm', 'scale_residual', 'drop_path_scale', 'attention',
-    'prepend_tokens', 'stitch_add', 'stitch_finalize',
+    'prepend_tokens', 'stitch_add', 'stitch_finalize', 'pyramid_pool', 'pyramid_concat', 'pyramid_expand', 'adaptive_avg_pool2d',
 ]
 
-_PARTS = (_base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention, stitch)
+_PARTS = (_base, streams, conv, norm, pointwise, losses, depthwise, hr, fuse, transform, augment, rownorm, attention, stitch, pyramid)
 for _m in _PARTS:            # later families win: conv.conv2d (the traceable wrapper) over nothing, pointwise.relu over _base's none
     for _k, _v in vars(_m).items():
         if not (_k.startswith('__') and _k.endswith('__')):

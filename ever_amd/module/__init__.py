@@ -16,6 +16,8 @@ from .fs_relation import FarSegHead, FarSegPPHead, FSRelation, FSRelationV2
 from .layers import (AdaptiveAvgPool2d, BatchNorm2d, Conv2d, ConvTranspose2d, HipSequential, LayerNorm, MaxPool2d, ReLU,
                      UpsamplingBilinear2d, to_hip)
 from .ops import Bf16compatible, ConvBlock, ConvUpsampling, DepthwiseConv2d, PoolBlock, SeparableConv2d, SeparableConvBlock
+from .ppm import PPMHead, PyramidPoolModule
+from .pspnet import PSPNet
 from .resnet import ResNetEncoder
 from .vit_encoder import ViTEncoder
 
@@ -26,4 +28,4 @@ __all__ = ['ResNetEncoder', 'FPN', 'AssymetricDecoder', 'FSRelation', 'FSRelatio
            'Deeplabv3pDecoder', 'Deeplabv3pHead', 'DeepLabV3Plus',
            'HighResolutionModule', 'HighResolutionNet', 'HRNetEncoder', 'SimpleFusion', 'HRNetHead', 'HRNetSeg',
            'Fusion', 'FastNormalizedFusionConv3x3', 'NormalizedFusionConv3x3', 'BiFPN',
-           'LayerNorm', 'ConvNeXtEncoder', 'dinov3', 'ViTEncoder']
+           'LayerNorm', 'ConvNeXtEncoder', 'dinov3', 'ViTEncoder', 'PyramidPoolModule', 'PPMHead', 'PSPNet']

@@ -167,9 +167,13 @@ class UpsamplingNearest2d(nn.UpsamplingNearest2d):
 
 class AdaptiveAvgPool2d(nn.AdaptiveAvgPool2d):
     def forward(self, x):
-        if _one(self.output_size) != 1:
-            raise NotImplementedError('ever_amd AdaptiveAvgPool2d: only output_size=1 is implemented')
-        return HF.global_avg_pool(x)
+        size = _one(self.output_size)
+        if size == 1:
+            return HF.global_avg_pool(x)
+        if not isinstance(size, int) or not 2 <= size <= HF.PPM_MAX_BIN:
+            raise NotImplementedError(f'ever_amd AdaptiveAvgPool2d: square output sizes 1 to {HF.PPM_MAX_BIN} are implemented, '
+                                      f'got {self.output_size}')
+        return HF.adaptive_avg_pool2d(x, size)
 
 
 class GroupNorm(nn.GroupNorm):

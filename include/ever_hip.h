@@ -678,6 +678,57 @@ int evk_stitch_finalize(float* acc, const float* count, int32_t C, int32_t H, in
 int evk_stitch_plan(const int64_t* records, int32_t M, int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, int32_t nchw,
                     int32_t* out);
 
+/* Pyramid pooling (csrc/ppm.hip; reference ppm.py:8-35, ops.py:89-100) — `torch.cat([x] + [F.interpolate(block_k(
+ * F.adaptive_avg_pool2d(x, b_k)), (H, W), mode='bilinear', align_corners=False) for k], dim=1)` as one read of x for all K
+ * pools, one write of the concat map, and both backward halves in gather form.  fp32 on NHWC memory, plain fp32 under every
+ * conv-math mode, no packed operands, no float atomics: two runs give the same bits.
+ * x: [N,H,W,C]; bins: K sizes b_k (HOST array, read during the call, as are the per-bin pointer tables p, dp, z, dz);
+ * p_k, dp_k: [N,b_k,b_k,C]; z_k, dz_k: [N,b_k,b_k,Cp]; cat, dcat: [N,H,W,C + K Cp].
+ * Scope: 1 <= K <= 4, 1 <= b_k <= 8 (b_k > H is legal, as in aten), C % 4 == 0, Cp % 4 == 0, N H W (C + K Cp) < 2^31 and
+ * fewer than 2^31 pooled elements, else EVK_E_UNSUPPORTED; null pointers, pointers off the 16-byte grid, non-positive sizes:
+ * EVK_E_INVALID; a workspace smaller than its query: EVK_E_WORKSPACE.  Every refusal comes before any launch.
+ *
+ * Window i of an axis of L pixels under bin b is [ws, we) = [floor(i L / b), ceil((i + 1) L / b)) (aten's adaptive window;
+ * the windows of one bin overlap where L % b != 0).
+ * evk_ppm_pool_fwd:  p_k[n,i,j,c] = (sum of x[n,y,x,c] over the window) / float((ye - ys)(xe - xs)), ONE division.  Order of
+ *   the sum: each axis is cut at the union of all bins' window edges (at most 63 cells per axis, a partition of the map).
+ *   A cell row [y0, y1) is shared by four row groups, group g takes rows y0 + g, y0 + g + 4, ...; a group adds its rows in
+ *   ascending y, each row of the cell in ascending x, from +0; the cell sum is ((g0 + g1) + g2) + g3.  A window's cells are
+ *   then added row-major from +0.  The cell sums [N, cells_y, cells_x, C] go to the workspace.
+ * evk_ppm_expand_fwd:  cat[n,y,x,0:C] = x[n,y,x,:] (copied bits);  cat[n,y,x,C + k Cp + c] = the bilinear
+ *   align_corners=False sample of z_k.  Per axis (b sources, L outputs), in fp32, every operation rounded on its own, no fma:
+ *     s = float(b) / float(L);  src = max(s * (float(y) + 0.5) - 0.5, 0);  i0 = min(int(src), b - 1);  i1 = i0 + (i0 < b - 1);
+ *     l1 = src - float(i0);  l0 = 1 - l1
+ *   value = l0y * (l0x * p00 + l1x * p01) + l1y * (l0x * p10 + l1x * p11); an axis whose taps coincide (i1 == i0)
+ *   contributes the tap itself, without a blend, so a bin of 1 is an exact broadcast (evk_broadcast_hw's bits).
+ *   C may be 0 here and in evk_ppm_expand_bwd (x NULL): the up-sampled maps alone.
+ * evk_ppm_expand_bwd:  dz_k[n,i,j,c] = sum over (y, x) of wy(y,i) wx(x,j) dcat[n,y,x,C + k Cp + c], w(y,i) = l0 where
+ *   i == i0 != i1, l1 where i == i1 != i0, 1 where i == i0 == i1, else 0.  Separable: t[n,y,j,c] = sum over x ascending of
+ *   (wx * dcat), each product rounded, from +0 (workspace [N,H,sum b,Cp]); dz = sum over y ascending of (wy * t), from +0.
+ *   One read of dcat's pooled slices for all K bins; the gradient of x through the concat is NOT written: it is dcat's
+ *   channel slice [0, C), a strided view the caller hands to evk_ppm_pool_bwd.
+ * evk_ppm_pool_bwd:  dx[n,y,x,c] = (dskip ? dskip[(n H W + y W + x) ld + c] : +0) + q_1 + q_2 + ..., q = dp_k[n,i,j,c] /
+ *   float(count of window (i,j)), one division each, added in the order: bins k ascending, the windows of bin k that hold
+ *   (y, x) row-major.  ld >= C, ld % 4 == 0 (EVK_E_INVALID otherwise).  One write of dx. */
+size_t evk_ppm_pool_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, const int32_t* bins, int32_t K);
+int evk_ppm_pool_fwd(const float* x, float* const* p, const int32_t* bins, int32_t K, int32_t N, int32_t H, int32_t W,
+                     int32_t C, void* workspace, size_t workspace_bytes, void* stream);
+int evk_ppm_pool_bwd(const float* const* dp, const int32_t* bins, int32_t K, const float* dskip, int32_t ld, float* dx,
+                     int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
+int evk_ppm_expand_fwd(const float* x, const float* const* z, const int32_t* bins, int32_t K, float* cat, int32_t N, int32_t H,
+                       int32_t W, int32_t C, int32_t Cp, void* stream);
+size_t evk_ppm_expand_bwd_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t Cp, const int32_t* bins,
+                                          int32_t K);
+int evk_ppm_expand_bwd(const float* dcat, float* const* dz, const int32_t* bins, int32_t K, int32_t N, int32_t H, int32_t W,
+                       int32_t C, int32_t Cp, void* workspace, size_t workspace_bytes, void* stream);
+/* Host only, no launch: the checks the four launchers make on a case (same return codes; Cp may be 0: the pools alone, or C: the expand alone) and
+ * the forms they take.  out[16] = { kernel form (0: cells + windows, the only one), bytes per load and store (16), cells per
+ * axis y, x, pool forward stage 1 workgroups, of which per cell row (channel chunks of 256), stage 2 workgroups (N sum b^2),
+ * workgroups of expand forward and of pool backward (one per pixel), expand backward stage 1 workgroups, of which per row
+ * (chunks of 1024 pooled channels), stage 2 workgroups, threads per workgroup, pool workspace bytes, expand backward workspace
+ * bytes, sum b, sum b^2 }.  A workspace of 2^31 bytes or more is refused here alone (EVK_E_UNSUPPORTED). */
+int evk_ppm_plan(int32_t N, int32_t H, int32_t W, int32_t C, int32_t Cp, const int32_t* bins, int32_t K, int32_t* out);
+
 /* F.adaptive_avg_pool2d(x, 1) — fs_relation.py:177. x: [N,HW,C] -> y: [N,C]. */
 int evk_gap_fwd(const float* x, float* y, int32_t N, int32_t HW, int32_t C, void* stream);
 int evk_gap_bwd(const float* dy, float* dx, int32_t N, int32_t HW, int32_t C, void* stream);

@@ -27,9 +27,9 @@ FAMILIES = (
     ('bn', 'BatchNorm (bn_* kernels; bench.py times C-ABI calls of 2-3 kernels each)', BN),
     ('resample_loss', 'bilinear resampling + pixel losses (bilinear_* / bce_* / dice_* / ce_* kernels and their finalisation)', RESAMPLE_LOSS),
     ('pointwise', 'other streaming kernels of the model (relation_* / nearest2x_* / gap_* / mean4 / ew / stem_s2d / maxpool / gn_* / concat / '
-                  'channel_scale / confusion / subsample2 / hr_fuse_* / d4_* / wfuse_* / augment_* / stitch_*)', ('^relation_', '^nearest2x_', '^gap_', '^mean4', '^ew_', '^stem_s2d_kernel', '^maxpool', '^gn_', '^concat2',
+                  'channel_scale / confusion / subsample2 / hr_fuse_* / d4_* / wfuse_* / augment_* / stitch_* / ppm_*)', ('^relation_', '^nearest2x_', '^gap_', '^mean4', '^ew_', '^stem_s2d_kernel', '^maxpool', '^gn_', '^concat2',
                                                 '^split2', '^channel_scale', '^confusion', '^nchw_', '^nhwc_', '^bias_rows', '^pad_channels', '^unpad_channels',
-                                                '^relu_bits_apply', '^subsample2', '^broadcast_hw', '^sum_hw', '^hr_fuse_', '^d4_', '^wfuse_', '^augment_', '^stitch_')),
+                                                '^relu_bits_apply', '^subsample2', '^broadcast_hw', '^sum_hw', '^hr_fuse_', '^d4_', '^wfuse_', '^augment_', '^stitch_', '^ppm_')),
     ('depthwise', 'depthwise convolution (depthwise_fwd / depthwise_bwd / depthwise_reduce kernels: exact fp32 on the vector ALUs)',
      ('^depthwise_',)),
     ('ln', 'row LayerNorm and layer-scale residual (ln_fwd / ln_bwd / ln_records_finalize, lscale_fwd / lscale_bwd kernels)',
