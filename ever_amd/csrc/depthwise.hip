@@ -1,6 +1,5 @@
-// Depthwise convolution (groups == Cin == Cout, channel multiplier 1) on the vector ALUs, and the broadcast of a 1x1 map
-// with its adjoint.  Reference call sites: ever/module/ops.py:25-42 (DepthwiseConv2d / SeparableConv2d), :89-100
-// (PoolBlock's interpolate of a 1x1 map).
+// Depthwise convolution (groups == Cin == Cout, channel multiplier 1) on the vector ALUs.  Reference call sites:
+// ever/module/ops.py:25-42 (DepthwiseConv2d / SeparableConv2d).
 //
 // A 3x3 depthwise convolution does 9 MACs per 8 bytes it moves: HBM-bound, so the arithmetic is exact fp32 FMA in every
 // conv-math mode, and the kernels below are built around the loads.
@@ -13,7 +12,7 @@
 //             depthwise_reduce_kernel then sums the records of all tiles in a fixed order.  No float atomics: two runs give
 //             the same bits.
 // Every element offset is 64-bit.
-#include "common.hpp"
+#include "stream_common.hpp"
 
 namespace evk {
 
@@ -40,8 +39,6 @@ struct DwArgs {
   int row_tiles, strip_groups;
 };
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ f32x4 fma4(f32x4 a, f32x4 b, f32x4 c) {
   return f32x4{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y), __builtin_fmaf(a.z, b.z, c.z),
                __builtin_fmaf(a.w, b.w, c.w)};
@@ -66,8 +63,7 @@ __device__ __forceinline__ f32x4 grad_at(const DwArgs& a, int64_t off) {
 
 }  // namespace
 
-// (the kernels live in evk:: itself, so that profiles name them evk::depthwise_* / evk::broadcast_hw_* / evk::sum_hw_*:
-// tools/families.py)
+// (the kernels live in evk:: itself, so that profiles name them evk::depthwise_*: tools/families.py)
 // ---------------------------------------------------------------------------------------------------------- forward
 // KW: kernel width; SW: stride along W; D1: dilation 1 along W (the input window of a strip is then a compile-time
 // register array).  Kernel height, vertical stride / dilation and padding are runtime values.
@@ -302,36 +298,6 @@ __global__ __launch_bounds__(256) void depthwise_reduce_kernel(const float* __re
   }
 }
 
-// ------------------------------------------------------------------------------------------ 1x1 map broadcast / sum
-// dst[n][p][c] = src[n][c]: the bilinear resize of a 1x1 map (every output pixel reads the one source pixel, weight 1)
-__global__ __launch_bounds__(256) void broadcast_hw_kernel(const float* __restrict__ src, float* __restrict__ dst,
-                                                           int64_t total4, int64_t HW, int C) {
-  const int C4 = C >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
-    const int cb = (int)(i % C4);
-    const int64_t n = i / ((int64_t)HW * C4);
-    st4(dst + i * 4, ld4(src + n * C + cb * 4));
-  }
-}
-// dst[n][c] = sum over p of src[n][p][c], in a fixed order (grid (ceil(C4 / tpc), N); rl pixel slices per channel group)
-__global__ __launch_bounds__(256) void sum_hw_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t HW,
-                                                     int C, int tpc, int rl) {
-  __shared__ f32x4 red[256];
-  const int C4 = C >> 2;
-  const int tc = threadIdx.x % tpc, tr = threadIdx.x / tpc;
-  const int cb = blockIdx.x * tpc + tc;
-  const int64_t n = blockIdx.y;
-  f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (cb < C4 && tr < rl)
-    for (int64_t p = tr; p < HW; p += rl) s += ld4(src + (n * HW + p) * C + cb * 4);
-  red[threadIdx.x] = s;
-  __syncthreads();
-  if (tr == 0 && cb < C4) {
-    for (int i = 1; i < rl; ++i) s += red[i * tpc + tc];
-    st4(dst + n * C + cb * 4, s);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------ host side
 namespace {
 
@@ -505,23 +471,4 @@ extern "C" int evk_depthwise_bwd(const evk_conv_desc* d, const float* dy, const 
                        st, (const float*)a.slab, dw, db, (int)tiles, taps, a.C);
   }
   return check_launch("depthwise_bwd");
-}
-
-extern "C" int evk_broadcast_hw(const float* src, float* dst, int32_t N, int64_t HW, int32_t C, void* stream) {
-  EVK_REQUIRE(src && dst && N > 0 && HW > 0 && C > 0 && C % 4 == 0, EVK_E_INVALID, "broadcast_hw: bad argument");
-  const int64_t total4 = (int64_t)N * HW * (C / 4);
-  const int64_t blocks = (total4 + 255) / 256;
-  hipLaunchKernelGGL(broadcast_hw_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
-                     (hipStream_t)stream, src, dst, total4, (int64_t)HW, C);
-  return check_launch("broadcast_hw");
-}
-
-extern "C" int evk_sum_hw(const float* src, float* dst, int32_t N, int64_t HW, int32_t C, void* stream) {
-  EVK_REQUIRE(src && dst && N > 0 && HW > 0 && C > 0 && C % 4 == 0, EVK_E_INVALID, "sum_hw: bad argument");
-  const int c4 = C / 4;
-  const int tpc = c4 < 8 ? c4 : 8;     // 8 channel groups x 32 pixel slices per workgroup (ASPP: 16 x 1024 x 256 in 128 groups)
-  const int rl = 256 / tpc;
-  hipLaunchKernelGGL(sum_hw_kernel, dim3((c4 + tpc - 1) / tpc, N), dim3(256), 0, (hipStream_t)stream, src, dst,
-                     (int64_t)HW, C, tpc, rl);
-  return check_launch("sum_hw");
 }

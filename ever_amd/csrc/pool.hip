@@ -1,6 +1,6 @@
 // Pools and selections of the EVer hot path on NHWC fp32 (gfx950): MaxPool 3x3 s2, the x2 sub-sampling of LastLevelMaxPool,
-// nearest x2 + lateral add and its adjoint, global average pool.  16-byte accesses along the channel axis (C % 4 == 0).
-// Reference call sites are cited per entry point in include/ever_hip.h.
+// nearest x2 + lateral add and its adjoint, global average pool, the broadcast of a 1x1 map and its adjoint.  16-byte
+// accesses along the channel axis (C % 4 == 0).  Reference call sites are cited per entry point in include/ever_hip.h.
 #include "stream_common.hpp"
 
 namespace evk {
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
       for (int kx = 0; kx < 3; ++kx) {
         const int ix = ox * 2 - 1 + kx;
         if ((unsigned)ix >= (unsigned)W) continue;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + (((size_t)n * H + iy) * W + ix) * C + cb * 4);
+        const f32x4 v = ld4(x + (((size_t)n * H + iy) * W + ix) * C + cb * 4);
         const int t = ky * 3 + kx;
         if (first) {
           best = v; bx = by = bz = bw = t; first = false;
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
       }
     }
     const size_t o = (((size_t)n * Ho + oy) * Wo + ox) * C + cb * 4;
-    *reinterpret_cast<f32x4*>(y + o) = best;
+    st4(y + o, best);
     *reinterpret_cast<uint32_t*>(code + o) = (uint32_t)bx | ((uint32_t)by << 8) | ((uint32_t)bz << 16) | ((uint32_t)bw << 24);
   }
 }
@@ -65,14 +65,14 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
         const uint32_t t = (uint32_t)(ky * 3 + kx);
         const size_t o = (((size_t)n * Ho + oy) * Wo + ox) * C + cb * 4;
         const uint32_t cd = *reinterpret_cast<const uint32_t*>(code + o);
-        const f32x4 d = *reinterpret_cast<const f32x4*>(dy + o);
+        const f32x4 d = ld4(dy + o);
         if ((cd & 0xff) == t) g.x += d.x;
         if (((cd >> 8) & 0xff) == t) g.y += d.y;
         if (((cd >> 16) & 0xff) == t) g.z += d.z;
         if ((cd >> 24) == t) g.w += d.w;
       }
     }
-    *reinterpret_cast<f32x4*>(dx + i * 4) = g;
+    st4(dx, i, g);
   }
 }
 
@@ -82,15 +82,12 @@ __global__ __launch_bounds__(256) void nearest2x_add_kernel(const float* __restr
                                                             float* __restrict__ out, int N, int H, int W, int C,
                                                             uint32_t* __restrict__ amax) {
   const int c4 = C >> 2;
-  const int Ht = H >> 1, Wt = W >> 1;
   const size_t total = (size_t)N * H * W * c4;
   uint32_t m = 0;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const NhwcElem e = nhwc_elem(i, H, W, c4);       // of out (the fine map)
-    const f32x4 t = *reinterpret_cast<const f32x4*>(top + (((size_t)e.n * Ht + (e.y >> 1)) * Wt + (e.x >> 1)) * C + e.cb * 4);
-    const f32x4 l = *reinterpret_cast<const f32x4*>(lateral + i * 4);
-    const f32x4 v = l + t;
-    *reinterpret_cast<f32x4*>(out + i * 4) = v;
+    const f32x4 v = ld4(lateral, i) + ld4(top, coarse_elem(e, H, W, c4, 1));
+    st4(out, i, v);
     m = abs4_bits(m, v);
   }
   if (amax) commit_absmax(amax, m);
@@ -103,11 +100,8 @@ __global__ __launch_bounds__(256) void nearest2x_bwd_kernel(const float* __restr
   const size_t total = (size_t)N * Ht * Wt * c4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const NhwcElem e = nhwc_elem(i, Ht, Wt, c4);     // of dtop (the coarse map)
-    const float* b = dout + (((size_t)e.n * H + 2 * e.y) * W + 2 * e.x) * C + e.cb * 4;
-    const f32x4 s = (*reinterpret_cast<const f32x4*>(b) + *reinterpret_cast<const f32x4*>(b + C)) +
-                    (*reinterpret_cast<const f32x4*>(b + (size_t)W * C) +
-                     *reinterpret_cast<const f32x4*>(b + (size_t)W * C + C));
-    *reinterpret_cast<f32x4*>(dtop + i * 4) = s;
+    const Quad q = quad_elems((size_t)e.n * H + 2 * e.y, 2 * e.x, W, c4, e.cb);
+    st4(dtop, i, quad_sum(ld4(dout, q.e00), ld4(dout, q.e01), ld4(dout, q.e10), ld4(dout, q.e11)));
   }
 }
 
@@ -123,41 +117,35 @@ __global__ __launch_bounds__(256) void subsample2_kernel(const float* __restrict
     const int n = e.n, y = e.y, x = e.x, cb = e.cb;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (!ADJ)
-      v = *reinterpret_cast<const f32x4*>(src + (((size_t)n * H + 2 * y) * W + 2 * x) * C + cb * 4);
+      v = ld4(src + (((size_t)n * H + 2 * y) * W + 2 * x) * C + cb * 4);
     else if (!(x & 1) && !(y & 1))
-      v = *reinterpret_cast<const f32x4*>(src + (((size_t)n * Ho + (y >> 1)) * Wo + (x >> 1)) * C + cb * 4);
-    *reinterpret_cast<f32x4*>(dst + i * 4) = v;
+      v = ld4(src + (((size_t)n * Ho + (y >> 1)) * Wo + (x >> 1)) * C + cb * 4);
+    st4(dst, i, v);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Global average pool: x [N][HW][C] -> y [N][C].  grid (ceil(c4/tpc), N)
+// The per-channel sums over the pixels of x [N][HW][C] and their adjoints, each a call of the shared body
+// (stream_common.hpp: sum_hw_body, broadcast_hw_body) under its own launch geometry, which fixes the summation order.
+// Global average pool: y [N][C] = mean over p of x[n][p][c]
 __global__ __launch_bounds__(256) void gap_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int HW, int C,
                                                       int tpc, int rl, float inv) {
-  __shared__ f32x4 red[256];
-  const int c4 = C >> 2;
-  const int tc = threadIdx.x % tpc, tr = threadIdx.x / tpc;
-  const int cb = blockIdx.x * tpc + tc;
-  const int n = blockIdx.y;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (cb < c4 && tr < rl)
-    for (int p = tr; p < HW; p += rl) s += *reinterpret_cast<const f32x4*>(x + ((size_t)n * HW + p) * C + cb * 4);
-  red[threadIdx.x] = s;
-  __syncthreads();
-  if (tr == 0 && cb < c4) {
-    for (int k = 1; k < rl; ++k) s += red[k * tpc + tc];
-    *reinterpret_cast<f32x4*>(y + (size_t)n * C + cb * 4) = s * inv;
-  }
+  sum_hw_body(x, y, HW, C, tpc, rl, inv);
 }
 __global__ __launch_bounds__(256) void gap_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int N,
                                                       int HW, int C, float inv) {
-  const int c4 = C >> 2;
-  const size_t total = (size_t)N * HW * c4;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int cb = (int)(i % c4);
-    const size_t n = i / ((size_t)HW * c4);
-    *reinterpret_cast<f32x4*>(dx + i * 4) = *reinterpret_cast<const f32x4*>(dy + n * C + cb * 4) * inv;
-  }
+  broadcast_hw_body(dy, dx, (size_t)N * HW * (C >> 2), (size_t)HW, C, inv);
+}
+// dst[n][p][c] = src[n][c]: the bilinear resize of a 1x1 map (every output pixel reads the one source pixel, weight 1;
+// reference ever/module/ops.py:89-100, PoolBlock's interpolate), and its adjoint dst[n][c] = sum over p of src[n][p][c].
+// x * 1.0f is x for every x.
+__global__ __launch_bounds__(256) void broadcast_hw_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                           int64_t total4, int64_t HW, int C) {
+  broadcast_hw_body(src, dst, total4, HW, C, 1.f);
+}
+__global__ __launch_bounds__(256) void sum_hw_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t HW,
+                                                     int C, int tpc, int rl) {
+  sum_hw_body(src, dst, HW, C, tpc, rl, 1.f);
 }
 
 }  // namespace evk
@@ -214,4 +202,23 @@ extern "C" int evk_gap_fwd(const float* x, float* y, int32_t N, int32_t HW, int3
 extern "C" int evk_gap_bwd(const float* dy, float* dx, int32_t N, int32_t HW, int32_t C, void* stream) {
   EVK_REQUIRE(dy && dx && nhwc4_ok(N, HW, 1, C), EVK_E_INVALID, "gap_bwd: bad argument");
   return launch_elems("gap_bwd", gap_bwd_kernel, (size_t)N * HW * (C / 4), stream, dy, dx, N, HW, C, 1.f / (float)HW);
+}
+
+extern "C" int evk_broadcast_hw(const float* src, float* dst, int32_t N, int64_t HW, int32_t C, void* stream) {
+  EVK_REQUIRE(src && dst && N > 0 && HW > 0 && C > 0 && C % 4 == 0, EVK_E_INVALID, "broadcast_hw: bad argument");
+  const int64_t total4 = (int64_t)N * HW * (C / 4);
+  const int64_t blocks = (total4 + 255) / 256;
+  hipLaunchKernelGGL(broadcast_hw_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
+                     (hipStream_t)stream, src, dst, total4, (int64_t)HW, C);
+  return check_launch("broadcast_hw");
+}
+
+extern "C" int evk_sum_hw(const float* src, float* dst, int32_t N, int64_t HW, int32_t C, void* stream) {
+  EVK_REQUIRE(src && dst && N > 0 && HW > 0 && C > 0 && C % 4 == 0, EVK_E_INVALID, "sum_hw: bad argument");
+  const int c4 = C / 4;
+  const int tpc = c4 < 8 ? c4 : 8;     // 8 channel groups x 32 pixel slices per workgroup (ASPP: 16 x 1024 x 256 in 128 groups)
+  const int rl = 256 / tpc;
+  hipLaunchKernelGGL(sum_hw_kernel, dim3((c4 + tpc - 1) / tpc, N), dim3(256), 0, (hipStream_t)stream, src, dst,
+                     (int64_t)HW, C, tpc, rl);
+  return check_launch("sum_hw");
 }

@@ -16,7 +16,7 @@
 // along y (ascending y); every output element has one owner.  Pool backward: a workgroup per pixel adds, onto the skip
 // gradient, dp / count of every window that holds the pixel: bins in order, windows row-major, one division per quotient.
 // No float atomics, the same bits every run; 16-byte accesses along the channel axis (C % 4 == 0, Cp % 4 == 0) throughout.
-#include "common.hpp"
+#include "stream_common.hpp"
 
 // every product and sum below is rounded on its own: the tests state the blend and the quotient sums bit for bit
 #pragma clang fp contract(off)
@@ -115,8 +115,6 @@ static int ppm_geom(const char* what, int N, int H, int W, int C, int Cp, const 
 static inline int64_t ppm_pool_ws_bytes(const PpmGeom& g, int N, int C) { return (int64_t)N * g.ncy * g.ncx * C * 4; }
 static inline int64_t ppm_expand_ws_bytes(const PpmGeom& g, int N, int H, int Cp) { return (int64_t)N * H * g.sumb * Cp * 4; }
 
-__device__ __forceinline__ f32x4 ppm_ld(const float* p, size_t e) { return *reinterpret_cast<const f32x4*>(p + e); }
-__device__ __forceinline__ void ppm_st(float* p, size_t e, const f32x4 v) { *reinterpret_cast<f32x4*>(p + e) = v; }
 __device__ __forceinline__ f32x4 ppm_scale(float a, const f32x4 v) { return f32x4{a * v.x, a * v.y, a * v.z, a * v.w}; }
 __device__ __forceinline__ f32x4 ppm_div(const f32x4 v, float d) {
   return f32x4{__fdiv_rn(v.x, d), __fdiv_rn(v.y, d), __fdiv_rn(v.z, d), __fdiv_rn(v.w, d)};
@@ -139,13 +137,13 @@ __global__ __launch_bounds__(kPpmThreads) void ppm_cells_kernel(const PpmGeom g,
       for (int y = y0 + grp; y < y1; y += 4) {
         const float* p = x + (((size_t)n * H + y) * W + x0) * C + c;
 #pragma unroll 4
-        for (int xx = x0; xx < x1; ++xx, p += C) acc = acc + *reinterpret_cast<const f32x4*>(p);
+        for (int xx = x0; xx < x1; ++xx, p += C) acc = acc + ld4(p);
       }
     part[cx & 1][grp][lane] = acc;
     __syncthreads();      // one barrier per cell: the other half of `part` is written next
     if (grp == 0 && on) {
       const f32x4 s = ((part[cx & 1][0][lane] + part[cx & 1][1][lane]) + part[cx & 1][2][lane]) + part[cx & 1][3][lane];
-      ppm_st(cells, ((size_t)row * g.ncx + cx) * C + c, s);
+      st4(cells + ((size_t)row * g.ncx + cx) * C + c, s);
     }
   }
 }
@@ -167,8 +165,8 @@ __global__ __launch_bounds__(kPpmThreads) void ppm_windows_kernel(const PpmGeom 
   for (int c = threadIdx.x * 4; c < C; c += kPpmThreads * 4) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int cy = cy0; cy < cy1; ++cy)
-      for (int cx = cx0; cx < cx1; ++cx) acc = acc + ppm_ld(cells, (((size_t)n * g.ncy + cy) * g.ncx + cx) * C + c);
-    ppm_st(p, (((size_t)n * b + i) * b + j) * C + c, ppm_div(acc, count));
+      for (int cx = cx0; cx < cx1; ++cx) acc = acc + ld4(cells + (((size_t)n * g.ncy + cy) * g.ncx + cx) * C + c);
+    st4(p + (((size_t)n * b + i) * b + j) * C + c, ppm_div(acc, count));
   }
 }
 
@@ -188,6 +186,14 @@ __device__ __forceinline__ f32x4 ppm_blend(float l0, const f32x4 a, float l1, co
   return ppm_scale(l0, a) + ppm_scale(l1, b);
 }
 
+// the pixel of a workgroup-per-pixel kernel: pix = (n * H + py) * W + px
+__device__ __forceinline__ void ppm_pixel(uint32_t pix, int H, int W, uint32_t& n, uint32_t& py, uint32_t& px) {
+  const uint32_t r = pix / (uint32_t)W;      // r = n * H + py
+  px = pix - r * (uint32_t)W;
+  n = r / (uint32_t)H;
+  py = r - n * (uint32_t)H;
+}
+
 // ---- expand forward: workgroup per pixel
 __global__ __launch_bounds__(kPpmThreads) void ppm_expand_fwd_kernel(const PpmGeom g, const float* __restrict__ x,
                                                                      const PpmPtrs z, float* __restrict__ cat, int H, int W,
@@ -195,8 +201,8 @@ __global__ __launch_bounds__(kPpmThreads) void ppm_expand_fwd_kernel(const PpmGe
   __shared__ int si[kPpmMaxBins][4];
   __shared__ float sl[kPpmMaxBins][4];
   const uint32_t pix = blockIdx.x;
-  const uint32_t r = pix / (uint32_t)W, px = pix - r * (uint32_t)W;      // r = n * H + y
-  const uint32_t n = r / (uint32_t)H, py = r - n * (uint32_t)H;
+  uint32_t n, py, px;
+  ppm_pixel(pix, H, W, n, py, px);
   if ((int)threadIdx.x < g.K) {
     const int k = threadIdx.x, b = ppm_bin(g, k);
     int y0, y1, x0, x1;
@@ -212,20 +218,20 @@ __global__ __launch_bounds__(kPpmThreads) void ppm_expand_fwd_kernel(const PpmGe
   const float* xi = x + (size_t)pix * C;
   for (int c = threadIdx.x * 4; c < ctot; c += kPpmThreads * 4) {
     if (c < C) {
-      ppm_st(o, c, ppm_ld(xi, c));
+      st4(o + c, ld4(xi + c));
       continue;
     }
     const int k = (c - C) / Cp, cc = (c - C) - k * Cp, b = ppm_bin(g, k);
     const int y0 = si[k][0], y1 = si[k][1], x0 = si[k][2], x1 = si[k][3];
     const float* zk = ppm_ptr(z, k) + (size_t)n * b * b * Cp + cc;
-    f32x4 top = ppm_ld(zk, (size_t)(y0 * b + x0) * Cp);
-    if (x1 != x0) top = ppm_blend(sl[k][2], top, sl[k][3], ppm_ld(zk, (size_t)(y0 * b + x1) * Cp));
+    f32x4 top = ld4(zk + (size_t)(y0 * b + x0) * Cp);
+    if (x1 != x0) top = ppm_blend(sl[k][2], top, sl[k][3], ld4(zk + (size_t)(y0 * b + x1) * Cp));
     if (y1 != y0) {
-      f32x4 bot = ppm_ld(zk, (size_t)(y1 * b + x0) * Cp);
-      if (x1 != x0) bot = ppm_blend(sl[k][2], bot, sl[k][3], ppm_ld(zk, (size_t)(y1 * b + x1) * Cp));
+      f32x4 bot = ld4(zk + (size_t)(y1 * b + x0) * Cp);
+      if (x1 != x0) bot = ppm_blend(sl[k][2], bot, sl[k][3], ld4(zk + (size_t)(y1 * b + x1) * Cp));
       top = ppm_blend(sl[k][0], top, sl[k][1], bot);
     }
-    ppm_st(o, c, top);
+    st4(o + c, top);
   }
 }
 
@@ -270,8 +276,8 @@ __global__ __launch_bounds__(kPpmThreads) void ppm_expand_bwd_rows_kernel(const 
   const int k = q / Cp, c = q - k * Cp, b = ppm_bin(g, k), ctot = C + g.K * Cp;
   const float* src = dcat + (size_t)r * W * ctot + C + q;
   float* dst = rows + ((size_t)r * g.sumb + ppm_boff(g, k)) * Cp + c;
-  ppm_fold_axis(b, W, [&](int xx) { return ppm_ld(src, (size_t)xx * ctot); },
-                [&](int j, const f32x4 v) { ppm_st(dst, (size_t)j * Cp, v); });
+  ppm_fold_axis(b, W, [&](int xx) { return ld4(src + (size_t)xx * ctot); },
+                [&](int j, const f32x4 v) { st4(dst + (size_t)j * Cp, v); });
 }
 
 // ---- expand backward, stage 2: a thread per (n, column jj of sum(b), 16-byte channel column)
@@ -291,8 +297,8 @@ __global__ __launch_bounds__(kPpmThreads) void ppm_expand_bwd_cols_kernel(const 
   const float* src = rows + ((size_t)n * H * g.sumb + jj) * Cp + c;
   float* dst = ppm_ptr(dz, k) + ((size_t)n * b * b + j) * Cp + c;
   const size_t ystride = (size_t)g.sumb * Cp;
-  ppm_fold_axis(b, H, [&](int y) { return ppm_ld(src, (size_t)y * ystride); },
-                [&](int i, const f32x4 v) { ppm_st(dst, (size_t)i * b * Cp, v); });
+  ppm_fold_axis(b, H, [&](int y) { return ld4(src + (size_t)y * ystride); },
+                [&](int i, const f32x4 v) { st4(dst + (size_t)i * b * Cp, v); });
 }
 
 // ---- pool backward: workgroup per pixel; the windows of bin k that hold row y are i = floor(y b / H) .. ceil((y + 1) b / H) - 1.
@@ -303,8 +309,8 @@ __global__ __launch_bounds__(kPpmThreads) void ppm_pool_bwd_kernel(const PpmGeom
   __shared__ int ext[kPpmMaxBins][2][kPpmMaxBin];      // rows (0) or columns (1) of window i of bin k
   __shared__ int rng[kPpmMaxBins][4];
   const uint32_t pix = blockIdx.x;
-  const uint32_t r = pix / (uint32_t)W, px = pix - r * (uint32_t)W;
-  const uint32_t n = r / (uint32_t)H, py = r - n * (uint32_t)H;
+  uint32_t n, py, px;
+  ppm_pixel(pix, H, W, n, py, px);
   if (threadIdx.x < kPpmMaxBins * 2 * kPpmMaxBin) {
     const int k = threadIdx.x >> 4, ax = (threadIdx.x >> 3) & 1, i = threadIdx.x & 7, b = ppm_bin(g, k);
     const int L = ax ? W : H;
@@ -317,7 +323,7 @@ __global__ __launch_bounds__(kPpmThreads) void ppm_pool_bwd_kernel(const PpmGeom
   }
   __syncthreads();
   for (int c = threadIdx.x * 4; c < C; c += kPpmThreads * 4) {
-    f32x4 acc = dskip ? ppm_ld(dskip, (size_t)pix * ld + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = dskip ? ld4(dskip + (size_t)pix * ld + c) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < kPpmMaxBins; ++k) {
       if (k >= g.K) break;
@@ -325,9 +331,9 @@ __global__ __launch_bounds__(kPpmThreads) void ppm_pool_bwd_kernel(const PpmGeom
       const float* dk = dp.p[k] + (size_t)n * b * b * C + c;
       for (int i = rng[k][0]; i <= rng[k][1]; ++i)
         for (int j = rng[k][2]; j <= rng[k][3]; ++j)
-          acc = acc + ppm_div(ppm_ld(dk, (size_t)(i * b + j) * C), (float)(ext[k][0][i] * ext[k][1][j]));
+          acc = acc + ppm_div(ld4(dk + (size_t)(i * b + j) * C), (float)(ext[k][0][i] * ext[k][1][j]));
     }
-    ppm_st(dx, (size_t)pix * C + c, acc);
+    st4(dx + (size_t)pix * C + c, acc);
   }
 }
 
@@ -338,6 +344,20 @@ static int ppm_ptrs(const char* what, const float* const* p, int K, PpmPtrs* a) 
     EVK_REQUIRE(p[k] && aligned16(p[k]), EVK_E_INVALID, "%s: map %d is a null pointer or off the 16-byte grid", what, k);
     a->p[k] = const_cast<float*>(p[k]);
   }
+  return EVK_OK;
+}
+
+// What every launcher starts with: the geometry (Cp == 0: the pool side), the K maps as a table and, for a call with a
+// workspace (ws_bytes >= 0), its size: the cells of the pool forward, the folded rows of the expand backward.
+static int ppm_setup(const char* what, int N, int H, int W, int C, int Cp, const int32_t* bins, int K, const float* const* maps,
+                     PpmGeom* g, PpmPtrs* a, int64_t ws_bytes = -1) {
+  int rc = ppm_geom(what, N, H, W, C, Cp, bins, K, g);
+  if (rc != EVK_OK) return rc;
+  rc = ppm_ptrs(what, maps, K, a);
+  if (rc != EVK_OK || ws_bytes < 0) return rc;
+  const int64_t need = Cp ? ppm_expand_ws_bytes(*g, N, H, Cp) : ppm_pool_ws_bytes(*g, N, C);
+  EVK_REQUIRE(ws_bytes >= need, EVK_E_WORKSPACE, "%s: workspace of %lld bytes, %lld are needed (%s)", what, (long long)ws_bytes,
+              (long long)need, Cp ? "evk_ppm_expand_bwd_workspace_bytes" : "evk_ppm_pool_workspace_bytes");
   return EVK_OK;
 }
 
@@ -389,15 +409,9 @@ extern "C" int evk_ppm_pool_fwd(const float* x, float* const* p, const int32_t* 
   EVK_REQUIRE(x && p && workspace && aligned16(x) && aligned16(workspace) && C > 0, EVK_E_INVALID,
               "ppm_pool_fwd: bad argument (null pointer or a pointer off the 16-byte grid)");
   PpmGeom g;
-  int rc = ppm_geom("ppm_pool_fwd", N, H, W, C, 0, bins, K, &g);
-  if (rc != EVK_OK) return rc;
   PpmPtrs out;
-  rc = ppm_ptrs("ppm_pool_fwd", p, K, &out);
+  int rc = ppm_setup("ppm_pool_fwd", N, H, W, C, 0, bins, K, p, &g, &out, (int64_t)workspace_bytes);
   if (rc != EVK_OK) return rc;
-  const int64_t need = ppm_pool_ws_bytes(g, N, C);
-  EVK_REQUIRE((int64_t)workspace_bytes >= need, EVK_E_WORKSPACE,
-              "ppm_pool_fwd: workspace of %lld bytes, %lld are needed (evk_ppm_pool_workspace_bytes)",
-              (long long)workspace_bytes, (long long)need);
   const int nchunk = ceil_div(C, kWave * 4);
   hipStream_t st = (hipStream_t)stream;
   float* cells = (float*)workspace;
@@ -414,15 +428,13 @@ extern "C" int evk_ppm_pool_bwd(const float* const* dp, const int32_t* bins, int
   EVK_REQUIRE(dp && dx && aligned16(dx) && aligned16(dskip) && C > 0, EVK_E_INVALID,
               "ppm_pool_bwd: bad argument (null pointer or a pointer off the 16-byte grid)");
   PpmGeom g;
-  int rc = ppm_geom("ppm_pool_bwd", N, H, W, C, 0, bins, K, &g);
+  PpmPtrs in;
+  const int rc = ppm_setup("ppm_pool_bwd", N, H, W, C, 0, bins, K, dp, &g, &in);
   if (rc != EVK_OK) return rc;
   EVK_REQUIRE(!dskip || (ld >= C && ld % 4 == 0), EVK_E_INVALID,
               "ppm_pool_bwd: pixel stride %d of the skip gradient (at least C = %d and a multiple of 4)", ld, C);
   EVK_REQUIRE(!dskip || (int64_t)N * H * W * ld < 0x80000000LL, EVK_E_UNSUPPORTED,
               "ppm_pool_bwd: N H W ld = %lld (fewer than 2^31 are implemented)", (long long)((int64_t)N * H * W * ld));
-  PpmPtrs in;
-  rc = ppm_ptrs("ppm_pool_bwd", dp, K, &in);
-  if (rc != EVK_OK) return rc;
   hipLaunchKernelGGL(ppm_pool_bwd_kernel, dim3((unsigned)((int64_t)N * H * W)), dim3(kPpmThreads), 0, (hipStream_t)stream, g, in,
                      dskip, ld, dx, H, W, C);
   return check_launch("ppm_pool_bwd");
@@ -433,10 +445,8 @@ extern "C" int evk_ppm_expand_fwd(const float* x, const float* const* z, const i
   EVK_REQUIRE((x || C == 0) && z && cat && aligned16(x) && aligned16(cat) && Cp > 0, EVK_E_INVALID,
               "ppm_expand_fwd: bad argument (null pointer, a pointer off the 16-byte grid or non-positive size)");
   PpmGeom g;
-  int rc = ppm_geom("ppm_expand_fwd", N, H, W, C, Cp, bins, K, &g);
-  if (rc != EVK_OK) return rc;
   PpmPtrs in;
-  rc = ppm_ptrs("ppm_expand_fwd", z, K, &in);
+  const int rc = ppm_setup("ppm_expand_fwd", N, H, W, C, Cp, bins, K, z, &g, &in);
   if (rc != EVK_OK) return rc;
   hipLaunchKernelGGL(ppm_expand_fwd_kernel, dim3((unsigned)((int64_t)N * H * W)), dim3(kPpmThreads), 0, (hipStream_t)stream, g, x,
                      in, cat, H, W, C, Cp);
@@ -448,15 +458,9 @@ extern "C" int evk_ppm_expand_bwd(const float* dcat, float* const* dz, const int
   EVK_REQUIRE(dcat && dz && workspace && aligned16(dcat) && aligned16(workspace) && Cp > 0, EVK_E_INVALID,
               "ppm_expand_bwd: bad argument (null pointer, a pointer off the 16-byte grid or non-positive size)");
   PpmGeom g;
-  int rc = ppm_geom("ppm_expand_bwd", N, H, W, C, Cp, bins, K, &g);
-  if (rc != EVK_OK) return rc;
   PpmPtrs out;
-  rc = ppm_ptrs("ppm_expand_bwd", dz, K, &out);
+  int rc = ppm_setup("ppm_expand_bwd", N, H, W, C, Cp, bins, K, dz, &g, &out, (int64_t)workspace_bytes);
   if (rc != EVK_OK) return rc;
-  const int64_t need = ppm_expand_ws_bytes(g, N, H, Cp);
-  EVK_REQUIRE((int64_t)workspace_bytes >= need, EVK_E_WORKSPACE,
-              "ppm_expand_bwd: workspace of %lld bytes, %lld are needed (evk_ppm_expand_bwd_workspace_bytes)",
-              (long long)workspace_bytes, (long long)need);
   const int rchunk = ceil_div((int64_t)K * Cp, kPpmThreads * 4);
   hipStream_t st = (hipStream_t)stream;
   float* rows = (float*)workspace;

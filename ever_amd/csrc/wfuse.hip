@@ -11,7 +11,7 @@
 // an LDS tree make one record per workgroup, a second, one-workgroup launch adds the records in double, in index order,
 // and applies the Jacobian of the normalisation: no float atomics, the same bits every run.
 // 16-byte accesses along the channel axis (C % 4 == 0) throughout.
-#include "common.hpp"
+#include "stream_common.hpp"
 
 // a * b + c stays two roundings here: the shifted term's gradient (w^ g00 + w^ g01) + (w^ g10 + w^ g11) is then bit for
 // bit what the same-resolution form followed by the unit-weight block sum gives.  The dots ask for their fmaf by name.
@@ -90,8 +90,6 @@ __device__ __forceinline__ f32x4 wf_scale(float a, const f32x4 v) { return f32x4
 __device__ __forceinline__ float wf_dot(float p, const f32x4 g, const f32x4 t) {
   return fmaf(g.w, t.w, fmaf(g.z, t.z, fmaf(g.y, t.y, fmaf(g.x, t.x, p))));
 }
-__device__ __forceinline__ f32x4 wf_ld(const float* p, size_t e) { return *reinterpret_cast<const f32x4*>(p + e * 4); }
-__device__ __forceinline__ void wf_st(float* p, size_t e, const f32x4 v) { *reinterpret_cast<f32x4*>(p + e * 4) = v; }
 
 // One thread per 16-byte element j of y.  NT is a template parameter so that the term tables are indexed by constants
 // (a runtime index would put them in scratch).
@@ -103,19 +101,15 @@ __global__ __launch_bounds__(kWfThreads) void wfuse_fwd_kernel(const WfTerms a, 
   if (j >= n4) return;
   float wh[NT];
   wfuse_normalise<NT>(weights, norm, eps, wh);
-  const uint32_t H = fH.div, W = fW.div;
-  const uint32_t pix = fdiv(j, fc4), cb = j - pix * fc4.div;
-  const uint32_t r = fdiv(pix, fW), px = pix - r * W;
-  const uint32_t n = fdiv(r, fH), py = r - n * H;
+  const NhwcElem e = nhwc_elem(j, fc4, fW, fH);
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < NT; ++k) {
-    const size_t e = a.shift[k] == 0 ? (size_t)j
-                                     : (((size_t)n * (H >> 1) + (py >> 1)) * (W >> 1) + (px >> 1)) * (size_t)(C >> 2) + cb;
-    const f32x4 p = wf_scale(wh[k], wf_ld(a.t[k], e));     // a zero weight still multiplies: an infinity gives its NaN
+    const size_t ek = a.shift[k] == 0 ? (size_t)j : coarse_elem(e, fH.div, fW.div, (size_t)(C >> 2), 1);
+    const f32x4 p = wf_scale(wh[k], ld4(a.t[k], ek));     // a zero weight still multiplies: an infinity gives its NaN
     v = k == 0 ? p : v + p;
   }
-  wf_st(y, j, v);
+  st4(y, j, v);
 }
 
 // The backward.  Item i is, with QUAD, the quad (n, qy, qx) at channel chunk cb — its index among the quads is also the
@@ -138,32 +132,32 @@ __global__ __launch_bounds__(kWfThreads) void wfuse_bwd_kernel(const WfTerms a, 
     if (QUAD) {
       const uint32_t q = fdiv(i, fc4), cb = i - q * c4;
       const uint32_t r = fdiv(q, fWq), qx = q - r * fWq.div;     // r = n * (H / 2) + qy: row 2 r of the [N * H, W] pixel grid
-      const size_t e00 = ((size_t)r * 2 * W + 2 * qx) * c4 + cb, e01 = e00 + c4, e10 = e00 + (size_t)W * c4, e11 = e10 + c4;
-      const f32x4 g00 = wf_ld(dy, e00), g01 = wf_ld(dy, e01), g10 = wf_ld(dy, e10), g11 = wf_ld(dy, e11);
+      const Quad e = quad_elems((size_t)r * 2, 2 * qx, W, c4, cb);
+      const f32x4 g00 = ld4(dy, e.e00), g01 = ld4(dy, e.e01), g10 = ld4(dy, e.e10), g11 = ld4(dy, e.e11);
 #pragma unroll
       for (int k = 0; k < NT; ++k) {
         if (a.shift[k] == 0) {
           if (a.d[k]) {
-            wf_st(a.d[k], e00, wf_scale(wh[k], g00)); wf_st(a.d[k], e01, wf_scale(wh[k], g01));
-            wf_st(a.d[k], e10, wf_scale(wh[k], g10)); wf_st(a.d[k], e11, wf_scale(wh[k], g11));
+            st4(a.d[k], e.e00, wf_scale(wh[k], g00)); st4(a.d[k], e.e01, wf_scale(wh[k], g01));
+            st4(a.d[k], e.e10, wf_scale(wh[k], g10)); st4(a.d[k], e.e11, wf_scale(wh[k], g11));
           }
-          if (DW) p[k] = wf_dot(wf_dot(wf_dot(wf_dot(p[k], g00, wf_ld(a.t[k], e00)), g01, wf_ld(a.t[k], e01)),
-                                       g10, wf_ld(a.t[k], e10)), g11, wf_ld(a.t[k], e11));
+          if (DW) p[k] = wf_dot(wf_dot(wf_dot(wf_dot(p[k], g00, ld4(a.t[k], e.e00)), g01, ld4(a.t[k], e.e01)),
+                                       g10, ld4(a.t[k], e.e10)), g11, ld4(a.t[k], e.e11));
         } else {
           if (a.d[k])
-            wf_st(a.d[k], i, (wf_scale(wh[k], g00) + wf_scale(wh[k], g01)) + (wf_scale(wh[k], g10) + wf_scale(wh[k], g11)));
+            st4(a.d[k], i, quad_sum(wf_scale(wh[k], g00), wf_scale(wh[k], g01), wf_scale(wh[k], g10), wf_scale(wh[k], g11)));
           if (DW) {
-            const f32x4 t = wf_ld(a.t[k], i);
+            const f32x4 t = ld4(a.t[k], i);
             p[k] = wf_dot(wf_dot(wf_dot(wf_dot(p[k], g00, t), g01, t), g10, t), g11, t);
           }
         }
       }
     } else {
-      const f32x4 g = wf_ld(dy, i);
+      const f32x4 g = ld4(dy, i);
 #pragma unroll
       for (int k = 0; k < NT; ++k) {
-        if (a.d[k]) wf_st(a.d[k], i, wf_scale(wh[k], g));
-        if (DW) p[k] = wf_dot(p[k], g, wf_ld(a.t[k], i));
+        if (a.d[k]) st4(a.d[k], i, wf_scale(wh[k], g));
+        if (DW) p[k] = wf_dot(p[k], g, ld4(a.t[k], i));
       }
     }
   }
@@ -193,7 +187,7 @@ __global__ __launch_bounds__(kWfThreads) void wfuse_dw_finalize_kernel(const flo
   const uint32_t lo = tid * per, hi = lo + per < nrec ? lo + per : nrec;
   double s[kWfMaxTerms] = {0.0, 0.0, 0.0, 0.0};
   for (uint32_t b = lo; b < hi; ++b) {
-    const f32x4 rec = wf_ld(records, b);
+    const f32x4 rec = ld4(records, b);
     s[0] += (double)rec.x; s[1] += (double)rec.y; s[2] += (double)rec.z; s[3] += (double)rec.w;
   }
 #pragma unroll
@@ -231,12 +225,9 @@ __global__ __launch_bounds__(kWfThreads) void wfuse_dw_finalize_kernel(const flo
 
 static int wfuse_terms(const char* what, const float* const* terms, const int32_t* shifts, float* const* dterms, int nterms,
                        int H, int W, WfTerms* a) {
+  const int rc = check_terms(what, terms, shifts, nterms, 1, H, W);
+  if (rc != EVK_OK) return rc;
   for (int k = 0; k < nterms; ++k) {
-    EVK_REQUIRE(!terms || terms[k], EVK_E_INVALID, "%s: term %d is a null pointer", what, k);
-    EVK_REQUIRE(shifts[k] == 0 || shifts[k] == 1, EVK_E_UNSUPPORTED, "%s: term %d has shift %d (0 and 1 are implemented)", what,
-                k, shifts[k]);
-    EVK_REQUIRE(shifts[k] == 0 || (H % 2 == 0 && W % 2 == 0), EVK_E_UNSUPPORTED,
-                "%s: H = %d, W = %d must be even (term %d has shift 1)", what, H, W, k);
     a->t[k] = terms ? terms[k] : nullptr;
     a->d[k] = dterms ? dterms[k] : nullptr;
     a->shift[k] = shifts[k];
@@ -277,32 +268,11 @@ extern "C" int evk_wfuse_fwd(const float* const* terms, const int32_t* shifts, i
   const uint32_t n4 = (uint32_t)((int64_t)N * H * W * (C / 4));
   const dim3 grid((n4 + kWfThreads - 1) / kWfThreads), block(kWfThreads);
   const FastDiv fc4 = make_fastdiv((uint32_t)(C / 4)), fW = make_fastdiv((uint32_t)W), fH = make_fastdiv((uint32_t)H);
-  hipStream_t st = (hipStream_t)stream;
-  switch (nterms) {
-    case 1: hipLaunchKernelGGL(wfuse_fwd_kernel<1>, grid, block, 0, st, a, weights, norm, eps, y, n4, fc4, fW, fH, C); break;
-    case 2: hipLaunchKernelGGL(wfuse_fwd_kernel<2>, grid, block, 0, st, a, weights, norm, eps, y, n4, fc4, fW, fH, C); break;
-    case 3: hipLaunchKernelGGL(wfuse_fwd_kernel<3>, grid, block, 0, st, a, weights, norm, eps, y, n4, fc4, fW, fH, C); break;
-    default: hipLaunchKernelGGL(wfuse_fwd_kernel<4>, grid, block, 0, st, a, weights, norm, eps, y, n4, fc4, fW, fH, C); break;
-  }
-  return check_launch("wfuse_fwd");
+  return pick<1, 2, 3, 4>(nterms, [&](auto NT) {
+    hipLaunchKernelGGL(wfuse_fwd_kernel<NT()>, grid, block, 0, (hipStream_t)stream, a, weights, norm, eps, y, n4, fc4, fW, fH, C);
+    return check_launch("wfuse_fwd");
+  });
 }
-
-namespace evk {
-template <int NT>
-static void wfuse_bwd_launch(bool quad, bool dw, dim3 grid, hipStream_t st, const WfTerms& a, const float* dy,
-                             const float* weights, int norm, float eps, float* records, uint32_t nitems, FastDiv fc4,
-                             FastDiv fWq, int W) {
-  const dim3 block(kWfThreads);
-  if (quad && dw)
-    hipLaunchKernelGGL((wfuse_bwd_kernel<NT, true, true>), grid, block, 0, st, a, dy, weights, norm, eps, records, nitems, fc4, fWq, W);
-  else if (quad)
-    hipLaunchKernelGGL((wfuse_bwd_kernel<NT, true, false>), grid, block, 0, st, a, dy, weights, norm, eps, records, nitems, fc4, fWq, W);
-  else if (dw)
-    hipLaunchKernelGGL((wfuse_bwd_kernel<NT, false, true>), grid, block, 0, st, a, dy, weights, norm, eps, records, nitems, fc4, fWq, W);
-  else
-    hipLaunchKernelGGL((wfuse_bwd_kernel<NT, false, false>), grid, block, 0, st, a, dy, weights, norm, eps, records, nitems, fc4, fWq, W);
-}
-}  // namespace evk
 
 extern "C" int evk_wfuse_bwd(const float* dy, const float* const* terms, const int32_t* shifts, int32_t nterms,
                              const float* weights, int32_t norm, float eps, float* const* dterms, float* dweights,
@@ -328,15 +298,17 @@ extern "C" int evk_wfuse_bwd(const float* dy, const float* const* terms, const i
   float* records = (float*)workspace;
   const dim3 grid((unsigned)pl.grid);
   const uint32_t nitems = (uint32_t)pl.items;
-  const bool quad = pl.quad != 0, dw = dweights != nullptr;
+  const bool dw = dweights != nullptr;
   hipStream_t st = (hipStream_t)stream;
-  switch (nterms) {
-    case 1: wfuse_bwd_launch<1>(quad, dw, grid, st, a, dy, weights, norm, eps, records, nitems, fc4, fWq, W); break;
-    case 2: wfuse_bwd_launch<2>(quad, dw, grid, st, a, dy, weights, norm, eps, records, nitems, fc4, fWq, W); break;
-    case 3: wfuse_bwd_launch<3>(quad, dw, grid, st, a, dy, weights, norm, eps, records, nitems, fc4, fWq, W); break;
-    default: wfuse_bwd_launch<4>(quad, dw, grid, st, a, dy, weights, norm, eps, records, nitems, fc4, fWq, W); break;
-  }
-  rc = check_launch("wfuse_bwd");
+  rc = pick<1, 2, 3, 4>(nterms, [&](auto NT) {
+    return pick<1, 0>(pl.quad, [&](auto QUAD) {
+      return pick<1, 0>(dw, [&](auto DW) {
+        hipLaunchKernelGGL((wfuse_bwd_kernel<NT(), QUAD() != 0, DW() != 0>), grid, dim3(kWfThreads), 0, st, a, dy, weights, norm,
+                           eps, records, nitems, fc4, fWq, W);
+        return check_launch("wfuse_bwd");
+      });
+    });
+  });
   if (rc != EVK_OK || !dw) return rc;
   hipLaunchKernelGGL(wfuse_dw_finalize_kernel, dim3(1), dim3(kWfThreads), 0, st, records, (uint32_t)pl.grid, nterms, weights, norm,
                      eps, records + pl.grid * kWfMaxTerms, dweights);

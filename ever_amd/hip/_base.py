@@ -303,6 +303,17 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def ptr_array(ts):
+    """host array of the tensors' device pointers, None a null pointer (a `const float* const*` argument: read at the call,
+    nothing goes to the device)"""
+    return (ctypes.c_void_p * len(ts))(*[_ptr(t) for t in ts])
+
+
+def i32_array(vs):
+    """host array of int32 (a `const int32_t*` argument)"""
+    return (ctypes.c_int32 * len(vs))(*vs)
+
+
 def _timed_call(family, nbytes, name, *args):
     """_C.call bracketed by HIP events when bench.py's KernelTimer is active (HBM-bound families:
     `nbytes` = algorithmic bytes of the call)."""
@@ -321,16 +332,29 @@ def _require_cuda(t, what):
         raise HipPathError(f'{what}: fp32 tensors required, got {t.dtype}')
 
 
+def _check_dim(t, what, dim=4, dims='4-D [N, C, H, W]'):
+    if t.dim() != dim:
+        raise HipPathError(f'{what}: a {dims} tensor is required, got {tuple(t.shape)}')
+
+
+def _check_4d(t, what):
+    _require_cuda(t, what)
+    _check_dim(t, what)
+
+
+def _refuse_packed(what, done, *ts):
+    if any(_is_packed(t) for t in ts):
+        raise HipPathError(f'{what}: a packed activation (one convolution\'s private operand) cannot be {done}')
+
+
 def _check_map(t, what, dim, dims, why_untraceable, done):
     """what the inference-side families (hip/transform.py, hip/stitch.py) ask of a tensor: fp32 on the GPU, `dim`-D, not
     packed, and no trace being recorded"""
     _require_cuda(t, what)
     if oplib.tracing():
         raise HipPathError(f'{what}: not traceable ({why_untraceable})')
-    if t.dim() != dim:
-        raise HipPathError(f'{what}: a {dims} tensor is required, got {tuple(t.shape)}')
-    if _is_packed(t):
-        raise HipPathError(f'{what}: a packed activation (one convolution\'s private operand) cannot be {done}')
+    _check_dim(t, what, dim, dims)
+    _refuse_packed(what, done, t)
 
 
 def _inference_only(what, *ts):

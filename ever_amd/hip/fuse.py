@@ -1,8 +1,6 @@
 """BiFPN family of the host wrappers (include/ever_hip.h: evk_wfuse_*; csrc/wfuse.hip): the learned weighted fusion node
 `sum_k w^_k x_k` of reference fpn.py:196-224 as one autograd node, a term that the reference up-samples first
 (nn.UpsamplingNearest2d, fpn.py:264-269, 290) entering as an index shift.  Part of the hip/functional.py facade."""
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -10,7 +8,10 @@ from torch.autograd.function import once_differentiable
 from .. import _C
 from . import oplib
 from .workspace import workspace
-from ._base import HipPathError, _is_packed, _ptr, _require_cuda, _stream, _timed_call, as_nhwc, empty_nhwc, materialize_lazy
+from ._base import (
+    HipPathError, _check_4d, _ptr, _refuse_packed, _stream, _timed_call, _require_cuda, as_nhwc, empty_nhwc, i32_array,
+    materialize_lazy, ptr_array,
+)
 
 __all__ = ['weighted_fuse', 'upsample_nearest2x', 'wfuse_stats', 'WFUSE_EPS', 'WFUSE_NORMS']
 
@@ -31,8 +32,7 @@ class _WFuseFn(Function):
         h, w = terms[0].shape[2] << shifts[0], terms[0].shape[3] << shifts[0]
         dev, st = terms[0].device, _stream()
         y = empty_nhwc(n, c, h, w, dev)
-        tp = (ctypes.c_void_p * nt)(*[t.data_ptr() for t in terms])
-        sh = (ctypes.c_int32 * nt)(*shifts)
+        tp, sh = ptr_array(terms), i32_array(shifts)
         # algorithmic bytes: every term once at its own size, y once
         nb = 4.0 * (sum(t.numel() for t in terms) + y.numel())
         _timed_call('wfuse', nb, 'evk_wfuse_fwd', tp, sh, nt, _ptr(weights), norm, eps, y.data_ptr(), n, h, w, c, st)
@@ -61,9 +61,8 @@ class _WFuseFn(Function):
         if want_w:
             ws_bytes = _C.load().evk_wfuse_workspace_bytes(n, h, w, c, nt)
             ws = workspace(dev, ws_bytes)
-        tp = (ctypes.c_void_p * nt)(*[t.data_ptr() for t in terms]) if want_w else None
-        sh = (ctypes.c_int32 * nt)(*shifts)
-        dp = (ctypes.c_void_p * nt)(*[_ptr(d) for d in dts])
+        tp = ptr_array(terms) if want_w else None
+        sh, dp = i32_array(shifts), ptr_array(dts)
         # algorithmic bytes: dy once, every requested gradient once, every term once if the weights want theirs
         nb = 4.0 * (dy.numel() + sum(d.numel() for d in dts if d is not None) + (sum(t.numel() for t in terms) if want_w else 0))
         _timed_call('wfuse', nb, 'evk_wfuse_bwd', dy.data_ptr(), tp, sh, nt, _ptr(weights), norm, eps, dp, _ptr(dw), _ptr(ws),
@@ -100,9 +99,7 @@ def weighted_fuse(terms, weights, norm_method='fast_normalize', eps=WFUSE_EPS):
         raise ValueError(f'weighted_fuse: norm_method must be one of {sorted(WFUSE_NORMS)}, got {norm_method!r}')
     ts, shifts = [], []
     for t, shift in terms:
-        _require_cuda(t, 'weighted_fuse')
-        if t.dim() != 4:
-            raise HipPathError(f'weighted_fuse: a 4-D [N, C, H, W] tensor is required, got {tuple(t.shape)}')
+        _check_4d(t, 'weighted_fuse')
         ts.append(t)
         shifts.append(int(shift))
     if weights is not None:
@@ -124,8 +121,7 @@ def weighted_fuse(terms, weights, norm_method='fast_normalize', eps=WFUSE_EPS):
         raise HipPathError(f'weighted_fuse: {c} channels: the fusion kernels move 16 bytes along the channel axis, the channel '
                            f'count must be a multiple of 4')
     ts = [as_nhwc(t, 'weighted_fuse') for t in ts]
-    if any(_is_packed(t) for t in ts):
-        raise HipPathError('weighted_fuse: a packed activation (one convolution\'s private operand) cannot be a term')
+    _refuse_packed('weighted_fuse', 'a term', *ts)
     if weights is not None and not weights.is_contiguous():
         weights = weights.contiguous()
     wfuse_stats['nodes'] += 1

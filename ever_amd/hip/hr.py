@@ -1,8 +1,6 @@
 """HRNet family of the host wrappers (include/ever_hip.h: evk_hr_fuse_*, evk_upsample_bilinear_slice_*): the multi-resolution
 exchange that ends a HighResolutionModule (reference _hrnet.py:377-397) as one autograd node per output, and the head's
 bilinear up-sampling straight into the concat buffer (hrnet_head.py:17-25).  Part of the hip/functional.py facade."""
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -11,8 +9,8 @@ from .. import _C
 from . import weight_planes
 from .workspace import workspace
 from ._base import (
-    HipPathError, _amax_out, _amax_zeroed, _f16x2, _is_packed, _mark_packed, _note_amax, _ptr, _require_cuda, _stream,
-    _take_parts, _timed_call, as_nhwc, empty_nhwc, materialize_lazy,
+    HipPathError, _amax_out, _amax_zeroed, _f16x2, _is_packed, _mark_packed, _note_amax, _ptr, _refuse_packed, _require_cuda,
+    _stream, _take_parts, _timed_call, as_nhwc, empty_nhwc, i32_array, materialize_lazy, ptr_array,
 )
 
 __all__ = ['hr_fuse', 'bilinear_concat', 'hr_fuse_stats']
@@ -55,9 +53,8 @@ class _HrFuseFn(Function):
         y = empty_nhwc(n, c, h, w, dev)
         bits = torch.empty((_C.load().evk_relu_bits_bytes(y.numel()) // 4,), device=dev, dtype=torch.int32)
         abits = _amax_zeroed(dev)        # the sum is the operand of the next module's convolutions
-        tp = (ctypes.c_void_p * nt)(*[t.data_ptr() for t in terms])
-        sp = (ctypes.c_void_p * nt)(*[None if s is None else s[2].data_ptr() for s in stats])
-        sh = (ctypes.c_int32 * nt)(*[k[0] for k in cfg])
+        tp, sh = ptr_array(terms), i32_array([k[0] for k in cfg])
+        sp = ptr_array([None if s is None else s[2] for s in stats])
         # algorithmic bytes: every term once at its own size, y and its bits
         nb = 4.0 * (sum(t.numel() for t in terms) + y.numel()) + 4.0 * bits.numel()
         _timed_call('hr_fuse', nb, 'evk_hr_fuse_fwd', tp, sh, sp, nt, y.data_ptr(), bits.data_ptr(), _ptr(abits), n, h, w, c, st)
@@ -161,8 +158,7 @@ def hr_fuse(terms):
                 bn_cfg = (parts, bn.running_mean if track else None, bn.running_var if track else None, bn.momentum, bn.eps)
             else:
                 mode, bn_cfg = _BN_RUNNING, (None, bn.running_mean, bn.running_var, bn.momentum, bn.eps)
-        if _is_packed(t):
-            raise HipPathError('hr_fuse: a packed activation (one convolution\'s private operand) cannot be a term')
+        _refuse_packed('hr_fuse', 'a term', t)
         ts.append(t)
         cfg.append((int(shift), mode, bn_cfg))
         affine += [bn.weight, bn.bias] if mode != _PLAIN else [None, None]

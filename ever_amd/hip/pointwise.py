@@ -1,7 +1,6 @@
 """Streaming layers of the host wrappers: ReLU, add, pools, nearest / bilinear resampling, global average pool, FS-Relation
 (reference fs_relation.py:56-73), BatchNorm + ReLU + classifier dot (fpn.py:163-193), the decoder's 4-way mean.  Part of
 the hip/functional.py facade."""
-import ctypes
 import os
 
 import torch
@@ -13,7 +12,7 @@ from . import timing, weight_planes
 from .workspace import workspace
 from ._base import (  # noqa: F401
     HipPathError, _AMAX_HANDOFF, _affine_grads, _amax_zeroed, _conv_out, _dx_scale, _hand_scale, _inherit_amax, _note_amax, _ptr,
-    _require_cuda, _same_shape_fake, _stream, _take_handoff, _take_parts, _timed_call, as_nhwc, empty_nhwc,
+    _require_cuda, _same_shape_fake, _stream, _take_handoff, _take_parts, _timed_call, as_nhwc, empty_nhwc, ptr_array,
 )
 from .streams import (  # noqa: F401
     _note_param_use,
@@ -264,9 +263,7 @@ def fs_relation(scene, content, feat):
     return _inherit_amax(_RelationFn.apply(scene, content, feat), feat)   # sigmoid(.) * feat
 
 
-def _scene_ptrs(ts):
-    """host array of the tensors' device pointers (evk_relation_scene_*: read at the call, nothing goes to the device)"""
-    return (ctypes.c_void_p * len(ts))(*[_ptr(t) for t in ts])
+_scene_ptrs = ptr_array      # the pointer tables of evk_relation_scene_* under the name the scene-MLP tests import
 
 
 def _grad_of_1x1(w):
@@ -290,7 +287,7 @@ class _SceneMlpFn(Function):
         h = torch.empty((levels, n, c), device=dev, dtype=torch.float32)
         o = torch.empty((levels, n, c), device=dev, dtype=torch.float32)
         w1, b1, w2, b2 = (params[i::4] for i in range(4))
-        _C.call('evk_relation_scene_fwd', s.data_ptr(), _scene_ptrs(w1), _scene_ptrs(b1), _scene_ptrs(w2), _scene_ptrs(b2),
+        _C.call('evk_relation_scene_fwd', s.data_ptr(), ptr_array(w1), ptr_array(b1), ptr_array(w2), ptr_array(b2),
                 h.data_ptr(), o.data_ptr(), levels, n, k, c, _stream())
         _note_param_use(*params)
         ctx.set_materialize_grads(False)      # (an output nobody used arrives as None = a null pointer = zeros in the kernels)
@@ -311,9 +308,9 @@ class _SceneMlpFn(Function):
         grads = [_grad_of_1x1(p) if p.dim() == 4 else torch.empty_like(p) for p in params]
         ws_bytes = _C.load().evk_relation_scene_bwd_workspace_bytes(levels, n, k, c)
         ws = workspace(dev, ws_bytes)
-        _C.call('evk_relation_scene_bwd', s.data_ptr(), h.data_ptr(), _scene_ptrs(gs), _scene_ptrs(w1), _scene_ptrs(w2),
-                dh.data_ptr(), ds.data_ptr(), _scene_ptrs(grads[0::4]), _scene_ptrs(grads[1::4]), _scene_ptrs(grads[2::4]),
-                _scene_ptrs(grads[3::4]), levels, n, k, c, ws.data_ptr(), ws_bytes, _stream())
+        _C.call('evk_relation_scene_bwd', s.data_ptr(), h.data_ptr(), ptr_array(gs), ptr_array(w1), ptr_array(w2),
+                dh.data_ptr(), ds.data_ptr(), ptr_array(grads[0::4]), ptr_array(grads[1::4]), ptr_array(grads[2::4]),
+                ptr_array(grads[3::4]), levels, n, k, c, ws.data_ptr(), ws_bytes, _stream())
         return (ds, *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[1:])])
 
 

@@ -2,8 +2,6 @@
 reference ppm.py:30-33 / ops.py:89-100 from one read of the map, and the K bilinear (align_corners=False) up-samplings
 with the channel concat as one write, each one autograd node whose backward is one gather-form call.  Part of the
 hip/functional.py facade."""
-import ctypes
-
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
@@ -12,20 +10,15 @@ from torch.autograd.function import once_differentiable
 from .. import _C
 from . import oplib
 from .workspace import workspace
-from ._base import HipPathError, _is_packed, _ptr, _require_cuda, _stream, _timed_call, as_nhwc, empty_nhwc, materialize_lazy
+from ._base import (
+    HipPathError, _check_4d, _ptr, _refuse_packed, _stream, _timed_call, as_nhwc, empty_nhwc, i32_array, materialize_lazy,
+    ptr_array,
+)
 
 __all__ = ['pyramid_pool', 'pyramid_concat', 'pyramid_expand', 'adaptive_avg_pool2d', 'check_bins', 'pyramid_stats', 'PPM_MAX_BINS', 'PPM_MAX_BIN']
 
 PPM_MAX_BINS, PPM_MAX_BIN = 4, 8                      # the scope of the kernels (include/ever_hip.h)
 pyramid_stats = {'pool': 0, 'concat': 0, 'skip_views': 0, 'aten': 0}      # tests / tools
-
-
-def _bins_arg(bins):
-    return (ctypes.c_int32 * len(bins))(*bins)
-
-
-def _ptrs(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
 
 def _skip_stride(g, c):
@@ -49,12 +42,12 @@ class _PyramidPoolFn(Function):
         n, c, h, w = x.shape
         dev, st, k = x.device, _stream(), len(bins)
         ps = [empty_nhwc(n, c, b, b, dev) for b in bins]
-        ba = _bins_arg(bins)
+        ba = i32_array(bins)
         ws_bytes = _C.load().evk_ppm_pool_workspace_bytes(n, h, w, c, ba, k)
         ws = workspace(dev, ws_bytes)
         # algorithmic bytes: x once, the pools once
         nb = 4.0 * (x.numel() + sum(p.numel() for p in ps))
-        _timed_call('ppm', nb, 'evk_ppm_pool_fwd', x.data_ptr(), _ptrs(ps), ba, k, n, h, w, c, ws.data_ptr(), ws_bytes, st)
+        _timed_call('ppm', nb, 'evk_ppm_pool_fwd', x.data_ptr(), ptr_array(ps), ba, k, n, h, w, c, ws.data_ptr(), ws_bytes, st)
         ctx.bins = bins
         ctx.dims = (n, c, h, w)
         return (x, *ps)
@@ -82,7 +75,7 @@ class _PyramidPoolFn(Function):
                 ld = c
         dx = empty_nhwc(n, c, h, w, dev)
         nb = 4.0 * (dx.numel() * (2 if dskip is not None else 1) + sum(g.numel() for g in dps))
-        _timed_call('ppm', nb, 'evk_ppm_pool_bwd', _ptrs(dps), _bins_arg(bins), k, None if dskip is None else dskip.data_ptr(), ld,
+        _timed_call('ppm', nb, 'evk_ppm_pool_bwd', ptr_array(dps), i32_array(bins), k, None if dskip is None else dskip.data_ptr(), ld,
                     dx.data_ptr(), n, h, w, c, st)
         return None, dx
 
@@ -99,7 +92,7 @@ class _PyramidConcatFn(Function):
         dev, st = zs[0].device, _stream()
         cat = empty_nhwc(n, c + k * cp, h, w, dev)
         nb = 4.0 * (n * h * w * c + sum(z.numel() for z in zs) + cat.numel())
-        _timed_call('ppm', nb, 'evk_ppm_expand_fwd', _ptr(x), _ptrs(zs), _bins_arg(bins), k, cat.data_ptr(), n, h, w, c, cp, st)
+        _timed_call('ppm', nb, 'evk_ppm_expand_fwd', _ptr(x), ptr_array(zs), i32_array(bins), k, cat.data_ptr(), n, h, w, c, cp, st)
         ctx.bins = bins
         ctx.dims = (n, c, h, w, cp)
         return cat
@@ -116,11 +109,11 @@ class _PyramidConcatFn(Function):
         dzs = [None] * k
         if any(ctx.needs_input_grad[3:]):
             dzs = [empty_nhwc(n, cp, b, b, dev) for b in bins]
-            ba = _bins_arg(bins)
+            ba = i32_array(bins)
             ws_bytes = _C.load().evk_ppm_expand_bwd_workspace_bytes(n, h, w, c, cp, ba, k)
             ws = workspace(dev, ws_bytes)
             nb = 4.0 * (n * h * w * k * cp + sum(z.numel() for z in dzs))
-            _timed_call('ppm', nb, 'evk_ppm_expand_bwd', dcat.data_ptr(), _ptrs(dzs), ba, k, n, h, w, c, cp, ws.data_ptr(), ws_bytes,
+            _timed_call('ppm', nb, 'evk_ppm_expand_bwd', dcat.data_ptr(), ptr_array(dzs), ba, k, n, h, w, c, cp, ws.data_ptr(), ws_bytes,
                         st)
             dzs = [z if need else None for z, need in zip(dzs, ctx.needs_input_grad[3:])]
         return (None, None, dx, *dzs)
@@ -139,12 +132,6 @@ def check_bins(bins, what='pyramid_pool'):
         raise NotImplementedError(f'ever_amd {what}: 1 to {PPM_MAX_BINS} bins of size 1 to {PPM_MAX_BIN} are implemented, '
                                   f'got {tuple(out)}')
     return tuple(out)
-
-
-def _check_4d(x, what):
-    _require_cuda(x, what)
-    if x.dim() != 4:
-        raise HipPathError(f'{what}: a 4-D [N, C, H, W] tensor is required, got {tuple(x.shape)}')
 
 
 def _in_scope(what, n, h, w, c, cp, k):
@@ -168,8 +155,7 @@ def pyramid_pool(x, bins):
     n, c, h, w = x.shape
     _in_scope('pyramid_pool', n, h, w, c, 0, len(bins))
     x = as_nhwc(x, 'pyramid_pool')
-    if _is_packed(x):
-        raise HipPathError('pyramid_pool: a packed activation (one convolution\'s private operand) cannot be pooled')
+    _refuse_packed('pyramid_pool', 'pooled', x)
     pyramid_stats['pool'] += 1
     return _PyramidPoolFn.apply(bins, x)
 
@@ -194,8 +180,7 @@ def pyramid_concat(x_pass, zs, bins=None):
     _in_scope('pyramid_concat', n, h, w, c, cp, len(bins))
     x_pass = as_nhwc(x_pass, 'pyramid_concat')
     zs = [as_nhwc(z, 'pyramid_concat') for z in zs]
-    if _is_packed(x_pass) or any(_is_packed(z) for z in zs):
-        raise HipPathError('pyramid_concat: a packed activation (one convolution\'s private operand) cannot be resampled')
+    _refuse_packed('pyramid_concat', 'resampled', x_pass, *zs)
     pyramid_stats['concat'] += 1
     return _PyramidConcatFn.apply(bins, (h, w), x_pass, *zs)
 
@@ -213,8 +198,7 @@ def pyramid_expand(z, size):
         return F.interpolate(z, (h, w), mode='bilinear', align_corners=False)
     _in_scope('pyramid_expand', z.shape[0], h, w, 0, z.shape[1], 1)
     z = as_nhwc(z, 'pyramid_expand')
-    if _is_packed(z):
-        raise HipPathError('pyramid_expand: a packed activation (one convolution\'s private operand) cannot be resampled')
+    _refuse_packed('pyramid_expand', 'resampled', z)
     return _PyramidConcatFn.apply(bins, (h, w), None, z)
 
 

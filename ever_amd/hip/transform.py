@@ -4,13 +4,13 @@ fused with the inverse transforms into one pass.  Part of the hip/functional.py 
 
 An op is 3 bits, `swap | flip_rows << 1 | flip_cols << 2`: transpose first, then flip.  Both wrappers take a tensor in
 either dense layout with no conversion: dense NHWC as it is, NCHW-contiguous as [N*C, H, W, 1] (the same memory)."""
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._base import _check_map, _inference_only, _ptr, _stream, _timed_call, empty_nhwc, is_nhwc, materialize_lazy, nhwc_copy
+from ._base import (
+    _check_map, _inference_only, _ptr, _stream, _timed_call, empty_nhwc, i32_array, is_nhwc, materialize_lazy, nhwc_copy, ptr_array,
+)
 
 __all__ = ['d4', 'd4_mean', 'd4_inverse', 'd4_compose', 'd4_out_hw', 'd4_stats', 'D4_IDENTITY', 'D4_TRANSPOSE', 'D4_VFLIP', 'D4_HFLIP',
            'D4_ROT90']
@@ -123,8 +123,7 @@ def d4_mean(terms, ops):
     with torch.no_grad():
         for i in range(0, len(ts), _MAX_TERMS):
             part, last = ts[i:i + _MAX_TERMS], i + _MAX_TERMS >= len(ts)
-            tp = (ctypes.c_void_p * len(part))(*[t.data_ptr() for t in part])
-            op = (ctypes.c_int32 * len(part))(*ops[i:i + _MAX_TERMS])
+            tp, op = ptr_array(part), i32_array(ops[i:i + _MAX_TERMS])
             # algorithmic bytes: every term once, y once (and the accumulator when the list is chained)
             nb = 4.0 * y.numel() * (len(part) + 1 + (1 if i else 0))
             _timed_call('resample_loss', nb, 'evk_d4_merge', tp, op, len(part), _ptr(y) if i else None, y.data_ptr(), nn, ho, wo,

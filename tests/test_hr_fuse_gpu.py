@@ -29,6 +29,8 @@ CASES = [
     ((3, 16, 24, 36), ((0, True), (0, False), (1, True), (2, True)), 'a lower output branch, N not a power of two'),
     ((2, 32, 32, 48), ((0, False), (1, True), (2, True), (3, True)), "W48's branch-0 form"),
     ((2, 8, 8, 8), ((0, False), (1, False)), 'the folded form with planted zeros'),
+    ((1, 4, 6, 4), ((0, True),), 'one term, less than one ReLU-bits chunk'),
+    ((2, 8, 12, 20), ((0, True), (1, False), (2, True)), 'three terms, CW = 5: 12 blocks per pool workgroup'),
 ]
 
 

@@ -152,3 +152,14 @@ def test_data_parallel_trainer_two_ranks_gloo(tmp_path):
     assert d0 == d1, 'replicas diverged: gradient all-reduce / broadcast broken'
     assert len(rec0) == 2 and len(rec1) == 0  # only the master logs
     assert all(0 < r['bce_loss'] < 2 for r in rec0)
+
+
+def test_ptr_array_and_i32_array_hold_what_the_c_abi_reads():
+    """hip/_base.py: the host arrays behind a `const float* const*` / `const int32_t*` argument — a tensor's data pointer,
+    a null pointer for None, the ints, with the lengths given"""
+    from ever_amd.hip._base import i32_array, ptr_array
+    t = torch.zeros((4,))
+    p = ptr_array([t, None])
+    assert len(p) == 2 and p[0] == t.data_ptr() and not p[1]
+    v = i32_array((0, 1))
+    assert len(v) == 2 and list(v) == [0, 1]
